@@ -1,9 +1,14 @@
 """Headline benchmark: decoded tokens/sec + acceptance rate of self-speculative decoding
 (llama2-7B shape, exit_layer=8, num_speculations=6, 512-token prompts, 512 new tokens, bf16, greedy)
-through the HIP engine, with the decode-bandwidth roofline, a per-kernel table, the reference algorithm on the same
-GPU (torch-ROCm eager) and a CPU baseline beside it.
+through the HIP engine.  A plain run sets up, warms up, times the steps and prints the line (plus the decode-bandwidth
+roofline of the timed steps' own traces, host arithmetic only); `--full` adds everything else: a per-kernel table, the
+gate/up roofline, the prefill leg, the engine's own autoregressive decoding, the sampled leg, the parity leg against the
+reference fixture, the reference algorithm on the same GPU (torch-ROCm eager), a CPU baseline, the extra operating
+points, the other model shapes and, on N > 1 GPUs, the replica throughput beside the pipeline.
 
     python bench.py --gpus 1 --steps 4 --warmup 1
+    python bench.py --gpus 1 --steps 4 --warmup 1 --full
+    python bench.py --gpus 1 --steps 4 --warmup 1 --dump-outputs DIR   # + DIR/<name>.npy of the last timed step
     python bench.py --gpus N ...                      # spawns N ranks itself (torch.distributed.run) when not under torchrun
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -11,9 +16,14 @@ GPU (torch-ROCm eager) and a CPU baseline beside it.
 A "step" is one `generate_token_ids` call: one synthetic 512-token prompt -> `max_steps` new tokens
 (reference benchmark.py:186-200 / generator_base.py:107-130).  Rank 0 prints ONE JSON line.
 
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step returned to its caller, as float64 arrays:
+DIR/predicted_tokens.npy (the new token ids), DIR/steps.npy ([num_drafts, num_matches] per speculation step) and
+DIR/acceptance_rate.npy (one value; absent for the autoregressive strategy).  The prompts and the weights are seeded, so
+the same arguments give the same inputs in every run.
+
 N = 1: the single-GPU engine (BASELINE config #2).  N > 1: the headline is the LAYER-RANGE PIPELINE of the same model over
 the N GPUs (north_star: rank 0 drafts on the early layers, the verify block streams through the other ranks; one
-sequence, "strong" scaling); the throughput of N independent replicas is reported beside it (`replicas`).
+sequence, "strong" scaling); with `--full` the throughput of N independent replicas is reported beside it (`replicas`).
 """
 from __future__ import annotations
 
@@ -77,6 +87,12 @@ def parse_args():
     ap.add_argument("--other-configs", default="llama3-8B,llama3.2-1B,llama2-13B")
     ap.add_argument("--graph-steps", action="store_true",
                     help="replay steady-state speculation steps from hipGraphs (LSK_OPT_GRAPH_STEPS; default off, DESIGN.md 3.3)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg (per-kernel table, gate/up roofline, prefill, autoregressive, sampled, "
+                         "reference parity, GPU reference, CPU baseline, operating points, other configs; the replicas beside the "
+                         "pipeline on N > 1 GPUs).  The --no-* options above select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (predicted_tokens, steps, acceptance_rate) as DIR/<name>.npy, float64")
     return ap.parse_args()
 
 
@@ -98,6 +114,56 @@ def step_bytes(cfg, exit_layer, prompt_len, trace):
         # verify: all layers + head once (prompt rows of the first step reuse the same weight pass)
         total += L * w_layer + w_head + L * kv_tok * (ctx + td)
     return total
+
+
+@torch.no_grad()
+def build_model_cpu_generator(cfg, seed, exit_layer, late_damping, dtype, device, init_std=0.02):
+    """`synthetic.build_model(..., gen_device="cpu")` with its parameters drawn side by side: every parameter has a CPU generator of
+    its own (synthetic._param_generator), so the bits are those of the one-at-a-time build (tests/test_bench_accounting.py checks
+    it) -- the checkpoint of tests/golden/full7b_rand_512.json -- in seconds instead of a minute at 7 B."""
+    from concurrent.futures import ThreadPoolExecutor
+    import transformers
+    cpu = torch.device("cpu")
+    with torch.device("meta"):
+        model = transformers.LlamaForCausalLM(cfg)
+    model.eval()
+    tied = bool(getattr(cfg, "tie_word_embeddings", False))
+    named = [(i, name, tuple(prm.shape)) for i, (name, prm) in enumerate(model.named_parameters())
+             if not (tied and name == "lm_head.weight")]
+
+    def draw(item):
+        index, name, shape = item
+        g = synthetic._param_generator(seed, index, cpu)
+        if len(shape) == 1:
+            value = 1.0 + 0.1 * torch.randn(shape, generator=g, device=cpu, dtype=torch.float32)
+        else:
+            value = init_std * torch.randn(shape, generator=g, device=cpu, dtype=torch.float32)
+            if exit_layer > 0 and (name.endswith("self_attn.o_proj.weight") or name.endswith("mlp.down_proj.weight")):
+                if int(name.split(".")[2]) >= exit_layer:
+                    value = value * late_damping
+        return name, value.to(dtype).to(device)
+
+    # one CPU generator draws serially: the parameters go to a pool sized like torch's own (OMP_NUM_THREADS where it is set)
+    with ThreadPoolExecutor(max_workers=max(1, min(32, torch.get_num_threads()))) as pool:
+        for name, value in pool.map(draw, named):
+            synthetic._assign(model, name, value)
+    if tied:
+        model.lm_head.weight = model.model.embed_tokens.weight
+    model.model.rotary_emb = type(model.model.rotary_emb)(cfg).to(device)
+    model.requires_grad_(False)
+    return model
+
+
+def dump_outputs(out_dir, result, steps):
+    """--dump-outputs: what one generation handed its caller, as float64 .npy files (token ids are exact in float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"predicted_tokens": np.asarray(result.predicted_tokens, dtype=np.float64),
+              "steps": np.asarray(steps, dtype=np.float64).reshape(-1, 2)}
+    if result.acceptance_rate is not None:
+        arrays["acceptance_rate"] = np.asarray([result.acceptance_rate], dtype=np.float64)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def self_spawn(args):
@@ -161,13 +227,16 @@ def main():
     cfg = synthetic.make_config(args.model)
     mode = args.parallelism
     if mode == "auto":
-        mode = "pp+replica" if (world > 1 and args.strategy == "self_speculative") else "replica"
+        if world > 1 and args.strategy == "self_speculative":
+            mode = "pp+replica" if args.full else "pp"
+        else:
+            mode = "replica"
     out = None
     if world > 1 and mode in ("pp", "pp+replica"):
         out = pipeline_bench(args, cfg, E, S, rank, world, dev, backend)
         torch.cuda.empty_cache()
     if mode in ("replica", "pp+replica"):
-        rep = replica_bench(args, cfg, E, S, rank, world, dev, backend, full=True)
+        rep = replica_bench(args, cfg, E, S, rank, world, dev, backend, full=args.full, headline=out is None)
         if out is None:
             out = rep
         elif rank == 0:
@@ -196,9 +265,9 @@ def _barrier(world):
     torch.cuda.synchronize()
 
 
-def replica_bench(args, cfg, E, S, rank, world, dev, backend, full):
-    """One engine per GPU, each decoding its own prompts.  `full`: this is the headline (N = 1, or --parallelism replica):
-    add the roofline, the per-kernel table and the baselines."""
+def replica_bench(args, cfg, E, S, rank, world, dev, backend, full, headline=True):
+    """One engine per GPU, each decoding its own prompts.  `full` (--full): add the per-kernel table, the gate/up roofline and the
+    other legs after the timed steps.  `headline`: this leg's last timed step is what --dump-outputs writes."""
     from layerskip_amd.engine import get_engine
     from layerskip_amd.hip_strategies import HipAutoRegressiveGenerationStrategy, HipSelfSpeculativeGenerationStrategy
     red_dev = dev if backend == "nccl" else torch.device("cpu")
@@ -212,9 +281,10 @@ def replica_bench(args, cfg, E, S, rank, world, dev, backend, full):
     #  the CPU-drawn bits only matter to the N = 1 line's reference_parity leg)
     cpu_weights = args.weights == "cpu" and n_params < 20e9 and world == 1
     if cpu_weights:
-        torch.set_num_threads(min(32, os.cpu_count() or 1))
-    model = synthetic.build_model(cfg, seed=0, exit_layer=E, late_damping=args.late_damping, dtype=torch.bfloat16,
-                                  device=dev, gen_device="cpu" if cpu_weights else dev)
+        model = build_model_cpu_generator(cfg, seed=0, exit_layer=E, late_damping=args.late_damping, dtype=torch.bfloat16, device=dev)
+    else:
+        model = synthetic.build_model(cfg, seed=0, exit_layer=E, late_damping=args.late_damping, dtype=torch.bfloat16,
+                                      device=dev, gen_device=dev)
     torch.cuda.synchronize()
     build_s = time.time() - t0
     big = n_params * 2 > 100e9      # > 100 GB of bf16: keep one copy only
@@ -282,6 +352,22 @@ def replica_bench(args, cfg, E, S, rank, world, dev, backend, full):
                        "host_occupancy": round(host["enqueue_s"] / max(host["wall_s"], 1e-9), 3),
                        "note": "time the one host thread spends enqueueing a speculation step (all its launches) vs the wall time of "
                                "the fused generate calls; the rest of the time it sleeps on the step event"}
+    if headline and rank == 0 and args.dump_outputs and results:
+        dump_outputs(args.dump_outputs, results[-1], step_traces[-1])
+    # ---- whole-path decode-bandwidth roofline from the run's own (T_d, n, ctx): host arithmetic on the timed steps' traces ----
+    if spec and rank == 0:
+        total_b, produced = 0, 0
+        for steps_i in step_traces:
+            trace, c, p = [], 0, args.prompt_len
+            for (td, n) in steps_i:
+                trace.append((c, p, td, n))
+                c, p = c + p + n, 1
+                produced += n + 1
+            total_b += step_bytes(cfg, E, args.prompt_len, trace)
+        floor_s = total_b / (HBM_PEAK_GBS * 1e9)
+        out["path_roofline"] = {"algorithmic_bytes_per_generation": total_b // max(1, len(step_traces)),
+                                "floor_tokens_per_s_at_8TBs": round(produced / floor_s, 1),
+                                "frac_of_floor": round((value / world) / (produced / floor_s), 4)}
     if not full or rank != 0:
         del engine, model
         return out
@@ -340,20 +426,6 @@ def replica_bench(args, cfg, E, S, rank, world, dev, backend, full):
             "rocprofv3_avg_launch_ms": rocprof_ms, "rocprofv3_source": rocprof_src,
             "rocprofv3_frac": None if not rocprof_ms else round(by / launches / (rocprof_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
         }
-    # ---- whole-path decode-bandwidth roofline from the run's own (T_d, n, ctx) ----
-    if spec:
-        total_b, produced = 0, 0
-        for steps_i in step_traces:
-            trace, c, p = [], 0, args.prompt_len
-            for (td, n) in steps_i:
-                trace.append((c, p, td, n))
-                c, p = c + p + n, 1
-                produced += n + 1
-            total_b += step_bytes(cfg, E, args.prompt_len, trace)
-        floor_s = total_b / (HBM_PEAK_GBS * 1e9)
-        out["path_roofline"] = {"algorithmic_bytes_per_generation": total_b // max(1, len(step_traces)),
-                                "floor_tokens_per_s_at_8TBs": round(produced / floor_s, 1),
-                                "frac_of_floor": round((value / world) / (produced / floor_s), 4)}
     if world == 1:
         out["prefill"] = prefill_leg(args, cfg, engine)
     if spec and world == 1:
@@ -677,6 +749,8 @@ def pipeline_bench(args, cfg, E, S, rank, world, dev, backend):
     hop_stats = [None] * world
     dist.all_gather_object(hop_stats, dec.stats())
     out = None
+    if rank == 0 and args.dump_outputs and results:
+        dump_outputs(args.dump_outputs, results[-1], results[-1].steps)
     if rank == 0:
         tokens = sum(len(r.predicted_tokens) for r in results)
         acc = [r.acceptance_rate for r in results if r.acceptance_rate is not None]

@@ -372,13 +372,12 @@ def _nccl_worker(rank, world, port, queue):
         dist.destroy_process_group()
 
 
-@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs >= 2 GPUs: one pipeline rank per device over RCCL")
 @pytest.mark.parametrize("world", [2, 4, 8])
 def test_pipeline_over_rccl_one_rank_per_gpu(world):
     """The transport the gloo twins stand in for, the first time a multi-GPU node runs this suite: backend nccl, one rank per
     device, rows sent straight from the engines' buffers -- token identity with the fused single-GPU engine."""
     if torch.cuda.device_count() < world:
-        pytest.skip(f"{world} GPUs needed")
+        pytest.skip(f"needs {world} GPUs (one pipeline rank per GPU over RCCL), found {torch.cuda.device_count()}")
     from layerskip_amd import GenerationConfig, synthetic
     from layerskip_amd.hip_strategies import HipSelfSpeculativeGenerationStrategy
     if world - 1 > synthetic.make_config("tiny-gqa").num_hidden_layers - 3:

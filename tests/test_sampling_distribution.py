@@ -1,18 +1,18 @@
 """Sampling path (`sample=True`, SSG:191-199 + LMU:124-131) "parity in distribution" (SURVEY.md 8f N2).
 
 The strategies' materialised-logits path is driven on CPU through the oracle-backed stage backend and
-compared with the UNMODIFIED reference's sampling run on the same weights.  The two consume random numbers in
-different orders, so the comparison is statistical: mean acceptance rate and the distribution of the first
-few generated tokens over many seeds.  Needs the reference tree (build container only)."""
+compared with the UNMODIFIED reference's sampling runs on the same weights, recorded in tests/golden/sampling/ref_runs.json
+(oracle/make_sampling_ref_runs.py: acceptance rate, first token and length of each of its N_RUNS seeded runs).  The two
+consume random numbers in different orders, so the comparison is statistical: mean acceptance rate and the distribution
+of the first few generated tokens over many seeds."""
 import collections
+import json
 import os
 
 import pytest
 import torch
 
-from conftest import build_case_model, load_golden
-
-pytestmark = pytest.mark.skipif(not os.path.isdir("/root/reference/self_speculation"), reason="reference tree not mounted")
+from conftest import GOLDEN_DIR, build_case_model, load_golden
 
 N_RUNS = 160
 
@@ -28,29 +28,19 @@ def test_sampled_speculation_matches_reference_in_distribution(monkeypatch, devi
     """host-sampling: the strategies' default `sample=True` path (logits materialised, torch draws).
     device-algorithm: the orchestration of lsk_spec_step_sampled with the oracle's draw-for-draw model of the two
     sampling kernels (key-space thresholds, Philox + Gumbel-max, rejection step) -- the algorithm the device runs."""
-    import copy
     from cpu_stage_backend import CpuStageBackend
     from layerskip_amd import GenerationConfig, hip_strategies
-    from oracle import ref_shim
-    ref = ref_shim.load_reference()
     rec = load_golden("tiny_mha_s1")
     base = build_case_model(rec).float()
     prompt, eos = rec["prompt"], rec["eos_token_ids"]
     E, S, T = rec["exit_layer"], 4, 10
     kw = dict(max_steps=T, exit_layer=E, num_speculations=S, sample=True, temperature=0.12, top_k=0, top_p=0.9)
 
-    ref_model = ref_shim.patch_model(copy.deepcopy(base))
-    ref_strat = ref.self_speculation_generator.SelfSpeculativeGenerationStrategy()
-    ref_cfg = ref.generator_base.GenerationConfig(**kw)
-    ref_acc, ref_first, ref_len = [], collections.Counter(), []
-    for i in range(N_RUNS):
-        torch.manual_seed(1000 + i)
-        with torch.inference_mode():
-            r = ref_strat.generate_token_ids(model=ref_model, input_ids=list(prompt), eos_token_ids=list(eos),
-                                             generation_config=ref_cfg)
-        ref_acc.append(r.acceptance_rate)
-        ref_first[r.predicted_tokens[0]] += 1
-        ref_len.append(len(r.predicted_tokens))
+    with open(os.path.join(GOLDEN_DIR, "sampling", "ref_runs.json")) as f:
+        runs = json.load(f)                     # the reference's runs on this fixture with exactly these settings
+    assert runs["fixture"] == "tiny_mha_s1" and runs["dtype"] == "fp32" and runs["n_runs"] == N_RUNS
+    assert {k: runs[k] for k in kw} == kw
+    ref_acc, ref_first, ref_len = runs["acceptance_rate"], collections.Counter(runs["first_token"]), runs["length"]
 
     backend = CpuStageBackend(base)
     monkeypatch.setattr(hip_strategies, "get_engine", lambda model, **k: backend)

@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 REPO=$PWD
 cd /tmp
-BENCH="python $REPO/bench.py --no-cpu-baseline --no-gpu-reference --no-sampled --no-operating-points --no-reference-parity --no-other-configs"
+BENCH="python $REPO/bench.py --full --no-cpu-baseline --no-gpu-reference --no-sampled --no-operating-points --no-reference-parity --no-other-configs"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o stats -- $BENCH --steps 2 --warmup 1 > "$OUT/stats_bench.log" 2>&1
 f=$(find /tmp/prof_stats -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$OUT/kernel_stats_7B_spec.csv"
 SHORT="$BENCH --weights gpu --steps 1 --warmup 0 --max-steps 48"

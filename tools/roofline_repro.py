@@ -19,7 +19,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["--weights", "gpu", "--no-cpu-baseline", "--no-gpu-reference", "--no-sampled", "--no-operating-points", "--no-reference-parity",
+FLAGS = ["--full", "--weights", "gpu", "--no-cpu-baseline", "--no-gpu-reference", "--no-sampled", "--no-operating-points", "--no-reference-parity",
          "--no-other-configs", "--steps", "2", "--warmup", "1"]
 
 
