@@ -33,14 +33,15 @@
 extern "C" {
 #endif
 
-#define LSK_ABI_VERSION 4   /* 2: options 4 / 6 removed, draft-block / sampled / profile-table entry points added, lsk_test_* moved to
+#define LSK_ABI_VERSION 5   /* 2: options 4 / 6 removed, draft-block / sampled / profile-table entry points added, lsk_test_* moved to
                              liblayerskip_hip_test.so (include/layerskip_hip_test.h), lsk_engine_weights_checksum added
                              3: sample=True on the layer pipeline (lsk_draft_block_sampled, lsk_pipeline_pack_sampled,
                              lsk_pipeline_tail_sampled, lsk_pipeline_residual, lsk_pipeline_result_words); message header 24 -> 40 words;
                              option 8 (the resident one-row grid) and lsk_engine_device_errors retired (profiles/r05_chain_resident_grid_retired.patch);
                              lsk_engine_set_globals accepts NULL embed / final_norm / lm_head (middle pipeline ranks)
                              4: LSK_MAX_EOS 8 -> 1024 (the reference folds any number of stop_token_ids into the eos list, generator_base.py:106;
-                             the workspace's eos region grew with it); vocabularies that are not a multiple of 16 documented as supported */
+                             the workspace's eos region grew with it); vocabularies that are not a multiple of 16 documented as supported
+                             5: sample=True autoregressive decoding on the device (lsk_ar_generate_sampled, lsk_ar_step_sampled) */
 #define LSK_MAX_ROWS 16
 #define LSK_MAX_SPEC 15   /* num_speculations handled by one fused step (rows = spec + 1) */
 #define LSK_MAX_EOS 1024   /* eos + stop token ids of one generation (generator_base.py:106); ids outside the vocabulary are dropped by the host */
@@ -288,6 +289,22 @@ int lsk_spec_generate_sampled(lsk_engine* e, const int32_t* prompt_ids, int32_t 
                               size_t scratch_bytes, int32_t* out_tokens, int32_t* n_out, int32_t* total_matches,
                               int32_t* total_drafts, int32_t* step_drafts, int32_t* step_matches, int32_t* n_steps,
                               void* stream);
+/* AutoRegressiveGenerationStrategy.generate_token_ids with sample=True (decode_next_token, llama_model_utils.py:123-131) and no
+ * logits processors.  DRAW CONTRACT: with key `seed` and counter base `offset`, token i is lsk_sample_rows' draw over that position's
+ * logits row at counter offset + i with tag0 = 32 (the verify tag) -- the draw step i of lsk_spec_generate_sampled makes with
+ * num_speculations = 0, and the one the layer pipeline's zero-speculation sampled step makes: all three give the same tokens.
+ * lsk_ar_step_sampled: one token (the sampled twin of lsk_ar_step: `forward` / `forward_early` up to layer_end over the new ids,
+ * then the draw at counter `offset`); only the token id comes back.  lsk_ar_generate_sampled: the whole generation in one call
+ * (lsk_ar_generate's structure: each drawn token's embedding is written into the next input row on the device, the host looks
+ * at the ids every 8 tokens, EOS is not emitted, the final context length is lsk_ar_generate's).  `scratch`:
+ * lsk_sampling_scratch_bytes() of device memory; out_tokens: host int32[max_steps]. */
+int lsk_ar_step_sampled(lsk_engine* e, const int32_t* input_ids, int32_t n_ids, int32_t layer_end, float temperature,
+                        int32_t top_k, float top_p, uint64_t seed, uint64_t offset, void* scratch, size_t scratch_bytes,
+                        int32_t* next_token, void* stream);
+int lsk_ar_generate_sampled(lsk_engine* e, const int32_t* input_ids, int32_t n_ids, int32_t layer_end,
+                            const int32_t* eos_token_ids, int32_t n_eos, int32_t max_steps, float temperature, int32_t top_k,
+                            float top_p, uint64_t seed, uint64_t offset, void* scratch, size_t scratch_bytes,
+                            int32_t* out_tokens, int32_t* n_out, void* stream);
 /* Final RMSNorm + lm_head (+ greedy argmax) over rows [row_base, row_base+m)
  * (llama_model_utils.py:204-205, :271-273, :386-387; decode_next_token :120-122).
  * logits_out: optional device fp32 [m][ld_logits] (values are bf16-rounded like the model dtype);

@@ -12,7 +12,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int32, c_size_t, c_uint64, c_vo
 LSK_MAX_ROWS = 16
 LSK_MAX_SPEC = 15
 LSK_MAX_EOS = 1024
-LSK_ABI_VERSION = 4
+LSK_ABI_VERSION = 5
 LSK_OPT_BIG_THRESHOLD = 1
 LSK_OPT_TARGET_WGS = 2
 LSK_OPT_FUSED_ATTN = 3
@@ -98,6 +98,10 @@ PROTOTYPES = {
                                             c_float, c_int32, c_float, c_uint64, c_uint64, c_void_p, c_size_t, POINTER(c_int32),
                                             POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
                                             POINTER(c_int32), c_void_p]),
+    "lsk_ar_step_sampled": (c_int32, [c_void_p, POINTER(c_int32), c_int32, c_int32, c_float, c_int32, c_float, c_uint64, c_uint64, c_void_p,
+                                      c_size_t, POINTER(c_int32), c_void_p]),
+    "lsk_ar_generate_sampled": (c_int32, [c_void_p, POINTER(c_int32), c_int32, c_int32, POINTER(c_int32), c_int32, c_int32, c_float, c_int32,
+                                          c_float, c_uint64, c_uint64, c_void_p, c_size_t, POINTER(c_int32), POINTER(c_int32), c_void_p]),
     "lsk_read_rows": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "lsk_write_rows": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "lsk_time_gateup": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_float), c_void_p]),

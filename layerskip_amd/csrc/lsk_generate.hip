@@ -641,6 +641,108 @@ extern "C" int lsk_spec_generate_sampled(lsk_engine* e, const int32_t* prompt_id
                               total_matches, total_drafts, step_drafts, step_matches, n_steps, stream, &sm);
 }
 
+// ---- sample=True autoregressive decoding (ARG:26-80 with decode_next_token(sample=True), LMU:123-131) ---------------------
+// DRAW CONTRACT.  In a sampled autoregressive generation with key `seed` and counter base `offset`, token i is the draw
+// lsk_sample_rows makes over that position's logits row at counter `offset + i` with tag0 = LSK_TAG_VERIFY (row 0 of the
+// draw).  That is exactly the draw step i of lsk_spec_generate_sampled makes with num_speculations = 0: nothing is drafted,
+// the verify block is the one input row at full depth, launch_sample(..., 1 row, LSK_TAG_VERIFY) at offset + i, and the
+// acceptance kernel emits that token unchanged.  So under one (seed, offset) the fused loop, the stepwise form and the layer
+// pipeline's zero-speculation sampled step (lsk_pipeline_tail_sampled) give the same tokens.
+//
+// The sampled head writes a logits row and has no argmax launch to carry the context advance of the greedy loop; the rows
+// therefore sit at pos_off = P - 1 + i over a context length that stays 0 (the same absolute positions: every kernel adds the two),
+// and the final length is set once at the end.
+static int ar_sampled_args(lsk_engine* e, const int32_t* input_ids, int32_t n_ids, int32_t layer_end) {
+    const lsk_config& c = e->cfg;
+    if (n_ids < 1 || n_ids - 1 > c.max_prompt) return lsk_fail("n_ids %d out of range", n_ids);
+    if (layer_end < 1 || layer_end > c.num_layers) return lsk_fail("layer_end %d out of range", layer_end);
+    LSK_TRY(lsk_layers_bound(e, 0, layer_end));
+    return lsk_check_ids(e, input_ids, n_ids);
+}
+
+// the prompt (all rows but the last) through layers [0, layer_end) and the last id's embedding into hrow[0]
+static int ar_prefill(lsk_engine* e, const int32_t* input_ids, int P, int layer_end, hipStream_t st) {
+    if (P > 1) HIP_OK(hipMemcpyAsync(e->bulk_ids, input_ids, sizeof(int) * (P - 1), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(e->row_tokens, input_ids + (P - 1), sizeof(int), hipMemcpyHostToDevice, st));
+    e->next_token_host = -1;
+    if (P > 1) {
+        LSK_TRY(lsk_embed_rows_dev(e, e->bulk_ids, P - 1, e->hbulk, st));
+        LSK_TRY(lsk_run_bulk_dev(e, P - 1, &e->state->kv_len, 0, layer_end, st));
+    }
+    return lsk_embed_rows_dev(e, e->row_tokens, 1, e->hrow, st);
+}
+
+extern "C" int lsk_ar_step_sampled(lsk_engine* e, const int32_t* input_ids, int32_t n_ids, int32_t layer_end, float temperature,
+                                   int32_t top_k, float top_p, uint64_t seed, uint64_t offset, void* scratch, size_t scratch_bytes,
+                                   int32_t* next_token, void* stream) {
+    LSK_TRY(lsk_ready(e));
+    hipStream_t st = (hipStream_t)stream;
+    if (!input_ids || !next_token) return lsk_fail("lsk_ar_step_sampled: null pointer");
+    LSK_TRY(ar_sampled_args(e, input_ids, n_ids, layer_end));
+    if (e->kv_len_host + n_ids > e->cfg.max_ctx) return lsk_fail("context overflow");
+    StepSampling sm;
+    LSK_TRY(make_step_sampling(e, temperature, top_k, top_p, seed, offset, scratch, scratch_bytes, &sm));
+    const int P = n_ids;
+    LSK_TRY(ar_prefill(e, input_ids, P, layer_end, st));
+    LSK_TRY(lsk_run_layers_dev(e, e->hrow, 1, &e->state->kv_len, P - 1, 0, layer_end, st));
+    LSK_TRY(lsk_run_head_dev(e, e->hrow, 1, sm.logits, sm.ld, nullptr, st));
+    LSK_TRY(launch_sample(e, sm.logits, sm.ld, 1, sm.temperature, sm.top_k, sm.top_p, sm.seed, sm.offset, LSK_TAG_VERIFY, e->verified,
+                          sm.p_verify, nullptr, st));
+    LSK_TRY(lsk_set_kv_len_dev(e, P, true, st));            // the context advances by the P new tokens, as in lsk_ar_step
+    HIP_OK(hipMemcpyAsync(next_token, e->verified, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// lsk_ar_generate with every argmax replaced by a draw: the drawn token's embedding goes straight into the input row of the next
+// token on the device; the host looks at the ids once per LSK_AR_BLOCK tokens.  Token i draws at counter offset + i.
+extern "C" int lsk_ar_generate_sampled(lsk_engine* e, const int32_t* input_ids, int32_t n_ids, int32_t layer_end, const int32_t* eos_token_ids,
+                                       int32_t n_eos, int32_t max_steps, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                                       uint64_t offset, void* scratch, size_t scratch_bytes, int32_t* out_tokens, int32_t* n_out, void* stream) {
+    LSK_TRY(lsk_ready(e));
+    hipStream_t st = (hipStream_t)stream;
+    const lsk_config& c = e->cfg;
+    if (!input_ids || !out_tokens || !n_out) return lsk_fail("lsk_ar_generate_sampled: null pointer");
+    if (max_steps < 1) return lsk_fail("max_steps %d < 1", max_steps);
+    if (n_eos < 0 || n_eos > LSK_MAX_EOS || (n_eos > 0 && !eos_token_ids)) return lsk_fail("bad eos list");
+    LSK_TRY(ar_sampled_args(e, input_ids, n_ids, layer_end));
+    if (n_ids + max_steps + LSK_AR_BLOCK > c.max_ctx) return lsk_fail("context overflow: %d + %d > max_ctx %d", n_ids, max_steps + LSK_AR_BLOCK, c.max_ctx);
+    if (!e->embed) return lsk_fail("lsk_ar_generate_sampled: the embedding is not bound on this engine");
+    StepSampling sm;
+    LSK_TRY(make_step_sampling(e, temperature, top_k, top_p, seed, offset, scratch, scratch_bytes, &sm));
+    LSK_TRY(lsk_engine_reset(e, stream));
+    const int P = n_ids;
+    LSK_TRY(ar_prefill(e, input_ids, P, layer_end, st));
+    const int* kvp = &e->state->kv_len;
+    int produced = 0;                   // tokens emitted so far = tokens drawn so far while no EOS has come back
+    bool done = false;
+    while (!done) {
+        const int blk = (max_steps - produced) < LSK_AR_BLOCK ? (max_steps - produced) : LSK_AR_BLOCK;
+        for (int i = 0; i < blk; ++i) {
+            const int t = produced + i;     // token index: its input row sits at position P - 1 + t
+            LSK_TRY(lsk_run_layers_dev(e, e->hrow, 1, kvp, P - 1 + t, 0, layer_end, st));
+            LSK_TRY(lsk_run_head_dev(e, e->hrow, 1, sm.logits, sm.ld, nullptr, st));
+            // token t -> verified[i], its embedding -> hrow[0] (the next input row)
+            LSK_TRY(launch_sample(e, sm.logits, sm.ld, 1, sm.temperature, sm.top_k, sm.top_p, sm.seed, sm.offset + (uint64_t)t, LSK_TAG_VERIFY,
+                                  e->verified + i, sm.p_verify, e->hrow, st));
+        }
+        HIP_OK(hipMemcpyAsync(e->host_result, e->verified, sizeof(int) * blk, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        for (int i = 0; i < blk && !done; ++i) {
+            const int tok = e->host_result[i];
+            for (int k = 0; k < n_eos; ++k)
+                if (tok == eos_token_ids[k]) done = true;          // EOS is not emitted (ARG:66-67)
+            if (!done) out_tokens[produced++] = tok;
+        }
+        if (produced >= max_steps) done = true;
+    }
+    // the verified context of lsk_ar_generate: prompt + emitted tokens minus the last one
+    LSK_TRY(lsk_set_kv_len_dev(e, P + (produced > 0 ? produced - 1 : 0), false, st));
+    HIP_OK(hipStreamSynchronize(st));
+    *n_out = produced;
+    return 0;
+}
+
 
 // ---- sample=True on the layer pipeline: the sampled step of enqueue_step_body split where its data lives (lsk_sample.h) -------------
 extern "C" int lsk_pipeline_result_words(const lsk_config* cfg, int32_t* out_words) {

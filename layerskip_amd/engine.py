@@ -438,6 +438,32 @@ class HipEngine:
                                    ctypes.byref(tok), self._stream))
         return tok.value
 
+    def ar_generate_sampled(self, input_ids: Sequence[int], layer_end: Optional[int], eos_token_ids: Sequence[int], max_steps: int,
+                            temperature: float, top_k: int, top_p: float, seed: int, offset: int) -> List[int]:
+        """Whole sample=True autoregressive generation in one C-ABI call (lsk_ar_generate_sampled): token i draws at Philox
+        counter offset + i, the draw step i of spec_generate_sampled makes with num_speculations = 0."""
+        ids = _i32_array(input_ids)
+        eos, eos_arr = self._eos_array(eos_token_ids)
+        out = (ctypes.c_int32 * max_steps)()
+        n_out = ctypes.c_int32(0)
+        scratch = self._sampling_scratch()
+        self._ck(self.lib.lsk_ar_generate_sampled(
+            self._handle, ids, len(input_ids), int(layer_end or self.num_layers), eos_arr, len(eos), int(max_steps), float(temperature),
+            int(top_k), float(top_p), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), scratch.data_ptr(), scratch.numel(), out,
+            ctypes.byref(n_out), self._stream))
+        return list(out[: n_out.value])
+
+    def ar_step_sampled(self, input_ids: Sequence[int], layer_end: Optional[int], temperature: float, top_k: int, top_p: float,
+                        seed: int, offset: int) -> int:
+        """One sample=True autoregressive token (lsk_ar_step_sampled), drawn at Philox counter `offset`; only the id comes back."""
+        ids = _i32_array(input_ids)
+        tok = ctypes.c_int32(0)
+        scratch = self._sampling_scratch()
+        self._ck(self.lib.lsk_ar_step_sampled(self._handle, ids, len(input_ids), int(layer_end or self.num_layers), float(temperature),
+                                           int(top_k), float(top_p), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
+                                           scratch.data_ptr(), scratch.numel(), ctypes.byref(tok), self._stream))
+        return tok.value
+
     # ------------------------------------------------------------------ layer-range pipeline (rank-0 half of a step)
     def draft_block(self, input_ids: Optional[Sequence[int]], row0: int, n_rows: int, pos_off0: int, exit_layer: int,
                     head_last: bool = False) -> None:

@@ -20,6 +20,9 @@ Execution paths:
         prefix match by modified rejection sampling ON THE DEVICE (`lsk_spec_generate_sampled` / `lsk_spec_step_sampled`):
         no logits row leaves HBM.  Parity with the reference is in distribution; the Philox stream is seeded from
         torch's generator (`torch.manual_seed(s)` reproduces a generation).
+  autoregressive  the same three paths for AutoRegressiveGenerationStrategy: `lsk_ar_generate` / `lsk_ar_step` greedy,
+        `lsk_ar_generate_sampled` / `lsk_ar_step_sampled` with `sample=True` (token i is the draw a zero-speculation sampled
+        step i makes under the same torch seed).
   slow  logits processors or more than 15 speculations: the same kernels driven row-block by row-block with the
         logits materialised as a tensor so the user's callables see what the reference shows them (sampling, if
         any, then happens on those logits with torch).
@@ -329,9 +332,14 @@ class HipSelfSpeculativeGenerationStrategy(GenerationStrategy):
 
 
 class HipAutoRegressiveGenerationStrategy(GenerationStrategy):
-    def __init__(self, engine_kwargs: Optional[dict] = None, fused_generate: bool = True) -> None:
+    def __init__(self, engine_kwargs: Optional[dict] = None, fused_generate: bool = True, device_sampling: bool = True) -> None:
         self.engine_kwargs = engine_kwargs or {}
         self.fused_generate = fused_generate
+        # device_sampling (default): `sample=True` without logits processors draws on the device (lsk_ar_generate_sampled /
+        # lsk_ar_step_sampled) -- no logits row leaves HBM.  Seeding contract of HipSelfSpeculativeGenerationStrategy: key =
+        # torch.initial_seed(), ONE 62-bit counter base per generation from torch's global generator, token i at base + i --
+        # the draws of a zero-speculation sampled generation under the same torch seed.
+        self.device_sampling = device_sampling
 
     # where the engine and the layers live (overridden by the layer pipeline's rank-0 slow path, layerskip_amd/pipeline_strategy.py)
     def _get_engine(self, model) -> HipEngine:
@@ -361,16 +369,31 @@ class HipAutoRegressiveGenerationStrategy(GenerationStrategy):
         layer_end = generation_config.exit_layer if generation_config.exit_layer > 0 else engine.num_layers
         if layer_end > engine.num_layers:
             raise ValueError(f"exit_layer={layer_end} > num_layers={engine.num_layers}")
-        if (self.fused_generate and not generation_config.sample and not logits_processors and not stopping_criteria
-                and streamer is None and hasattr(engine, "ar_generate")):
+        device_sampled = bool(generation_config.sample and self.device_sampling and not logits_processors
+                              and hasattr(engine, "ar_step_sampled"))
+        if device_sampled:
+            g = generation_config
+            sampling = (float(g.temperature), int(g.top_k), float(g.top_p), int(torch.initial_seed()),
+                        int(torch.randint(0, 2 ** 62, (1,)).item()))
+        unattended = self.fused_generate and not logits_processors and not stopping_criteria and streamer is None
+        if unattended and not generation_config.sample and hasattr(engine, "ar_generate"):
             tokens = engine.ar_generate([int(t) for t in input_ids], layer_end, eos_token_ids, generation_config.max_steps)
+            return GenerationStrategyResult(predicted_tokens=tokens, acceptance_rate=None)
+        if unattended and device_sampled and hasattr(engine, "ar_generate_sampled"):
+            tokens = engine.ar_generate_sampled([int(t) for t in input_ids], layer_end, eos_token_ids, generation_config.max_steps,
+                                                *sampling)
             return GenerationStrategyResult(predicted_tokens=tokens, acceptance_rate=None)
         cur = [int(t) for t in input_ids]
         cur_t = torch.tensor([cur])
         output_ids: List[int] = []
         slow = bool(logits_processors) or generation_config.sample
-        for _ in range(generation_config.max_steps):
-            if slow:
+        for i in range(generation_config.max_steps):
+            if device_sampled:
+                # (streamer / stopping criteria: one C-ABI call per token, the draw on the device, only the id comes back)
+                temperature, top_k, top_p, seed, base = sampling
+                tok = engine.ar_step_sampled(cur, layer_end, temperature, top_k, top_p, seed, base + i)
+                tok_t = torch.tensor([tok])
+            elif slow:
                 tok_t = self._slow_next(engine, cur, cur_t, layer_end, generation_config, logits_processors)
                 tok = int(tok_t.item())
             else:

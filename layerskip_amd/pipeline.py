@@ -63,6 +63,7 @@ _MAX_ROWS = 16
 _MAX_EOS = 1024    # LSK_MAX_EOS (include/layerskip_hip.h): eos + stop token ids of one generation
 _RES_WORDS = 24     # of the result block: num_matches, num_drafts, next token, context length, emitted[17]
 RES_PENDING, RES_ERROR = 21, 22     # sampled result block (csrc/lsk_sample.h): residual draw pending, protocol error
+RES_QROW = 64       # sampled result block: where q_n starts (LSK_PRES_QROW); a zero-speculation step never rejects and sends the words only
 # header words (layerskip_amd/csrc/lsk_accept.h); a host reads the first HDR_WORDS back
 HDR_MAGIC, HDR_GO, HDR_P, HDR_ROWS, HDR_KV, HDR_DRAFTS, HDR_MODE, HDR_OFF_LO, HDR_OFF_HI, HDR_WORDS = 0, 1, 2, 3, 4, 5, 21, 22, 23, 24
 HDR_MAGIC_VALUE = 0x4C534B31
@@ -295,6 +296,8 @@ class PipelineSpeculativeDecoder:
             elif mode == MODE_SAMPLED:
                 res = be.pipeline_tail_sampled(S + 1, sampling.temperature, sampling.top_k, sampling.top_p, sampling.seed,
                                                sampling.offset + step)
+                if S == 0:
+                    res = res[:RES_QROW]                     # no draft, no rejection, no residual: q_n is never needed
                 dist.send(res if self.direct else res.to(self.dev), dst=0, group=self.group)
             else:
                 res = be.pipeline_tail(S + 1)                # head + argmax + acceptance kernel -> device result block
@@ -353,7 +356,7 @@ class PipelineSpeculativeDecoder:
         if self._mode == MODE_LOGITS:
             t = torch.zeros(self._inflight_rows, be.vocab, dtype=getattr(be, "dtype", torch.float32), device=self.dev)
         elif self._mode == MODE_SAMPLED:
-            t = torch.zeros(be.pipeline_result_words(), dtype=torch.int32, device=self.dev)
+            t = torch.zeros(be.pipeline_result_words() if self._S > 0 else RES_QROW, dtype=torch.int32, device=self.dev)
         else:
             t = torch.zeros(_RES_WORDS, dtype=torch.int32, device=self.dev)
         dist.recv(t, src=self.world - 1, group=self.group)
@@ -363,10 +366,13 @@ class PipelineSpeculativeDecoder:
     def _result(self, local, row_base: int = 0, offset: Optional[int] = None) -> List[int]:
         if self._mode == MODE_SAMPLED:
             blk = local if local is not None else self._answer().to(self.be.device)
-            self.be.pipeline_residual(blk, row_base, self._sampling.seed, offset)      # no-op unless a rejection left the draw pending
+            if self._S > 0:
+                self.be.pipeline_residual(blk, row_base, self._sampling.seed, offset)  # no-op unless a rejection left the draw pending
             res = [int(v) for v in blk[:_RES_WORDS].tolist()]
             if res[RES_ERROR]:
                 raise RuntimeError("pipeline out of step: the last rank's Philox offset is not the header's")
+            if self._S == 0 and res[RES_PENDING]:
+                raise RuntimeError("pipeline result block: a residual draw is pending after a step without drafts")
             return res
         if local is not None:
             return [int(v) for v in local[:_RES_WORDS].tolist()]

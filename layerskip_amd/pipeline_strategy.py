@@ -19,6 +19,9 @@ MI355X-native partition instead: every rank stays, owns a contigu
            logits rows fetched from the last rank.
 `HipPipelineAutoRegressiveGenerationStrategy` is the same pipeline with zero speculations (one token per round trip: ARG:26-80 over
 a model that does not fit one GPU); early-exit-only decoding (ARG:44-51) runs rank-locally on rank 0, which owns those layers.
+Sampled autoregressive decoding is the zero-speculation sampled step (the last rank draws, the answer is the result words only) when
+rank 0's backend also offers `ar_generate_sampled` -- the one-GPU strategy then draws the same tokens on the device; over any other
+backend it stays on the host path of the one-GPU strategy for that backend.
 Streamers (both protocols) and stopping criteria are served per step on rank 0.
 """
 from __future__ import annotations
@@ -119,7 +122,7 @@ class _Rank0SlowARStrategy(HipAutoRegressiveGenerationStrategy):
     rank 0's layers locally, the rest and the head through `remote_verify` (one row per round trip)."""
 
     def __init__(self, dec: PipelineSpeculativeDecoder) -> None:
-        super().__init__(fused_generate=False)
+        super().__init__(fused_generate=False, device_sampling=False)      # rank 0's engine owns only the first layers
         self._dec = dec
 
     def _get_engine(self, model):
@@ -234,8 +237,10 @@ class HipPipelineSelfSpeculativeGenerationStrategy(GenerationStrategy):
 
             return dec.generate([int(t) for t in input_ids], eos, int(cfg.max_steps), S, driver=driver, prompt_rows=True)
         sampling = None
-        if generation_config.sample and not self.speculative:
-            # sampled autoregressive decoding: one logits row per round trip, drawn with torch on rank 0 (the one-GPU strategy's path)
+        if generation_config.sample and not self.speculative and not hasattr(dec.be, "ar_generate_sampled"):
+            # sampled autoregressive decoding over a backend whose one-GPU strategy samples on the host: one logits row per round trip,
+            # drawn with torch on rank 0 (that strategy's path, so that both give the same tokens).  A backend that draws on the device
+            # (HipEngine) takes the zero-speculation sampled step below: the last rank draws, rank 0 receives a token
             inner, cfg = self._slow_strategy(dec), generation_config
             return dec.generate([int(t) for t in input_ids], eos, int(cfg.max_steps), S,
                                 driver=lambda _dec: inner.generate_token_ids(model, input_ids, eos, cfg, logits_processors,
