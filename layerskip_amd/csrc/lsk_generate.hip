@@ -56,19 +56,19 @@ static int sample_sequence_status(lsk_engine* e, hipStream_t st) {
     return lsk_fail("sample=True: a launch of the draw sequence failed: %s (sampling state cleared)", hipGetErrorString(err));
 }
 
-static int launch_sample(lsk_engine* e, const float* logits, int ld, int m, float temperature, int top_k, float top_p, uint64_t seed,
-                         uint64_t offset, int tag0, int* tokens_dev, float* probs, elem_t* embed_dst, hipStream_t st) {
+// m rows of sm.logits drawn at Philox counter sm.offset with tags tag0, tag0 + 1, ...: tokens -> tokens_dev, warped distributions -> probs
+static int launch_sample(lsk_engine* e, const StepSampling& sm, int m, int tag0, int* tokens_dev, float* probs, elem_t* embed_dst, hipStream_t st) {
     // (lsk_engine_set_globals accepts a NULL embedding -- a pipeline rank that embeds nothing; a draw that is to leave its token's embedding
     // row behind needs one)
     if (embed_dst != nullptr && !e->embed) return lsk_fail("sample=True: the embedding is not bound on this engine (only rank 0 of a pipeline drafts)");
     SampleParams sp{};
-    sp.logits = logits; sp.ld = ld; sp.vocab = e->cfg.vocab; sp.inv_temperature = 1.0f / temperature;
-    sp.top_k = top_k; sp.top_p = top_p;
-    sp.seed_lo = (unsigned int)seed; sp.seed_hi = (unsigned int)(seed >> 32);
-    sp.off_lo = (unsigned int)offset; sp.off_hi = (unsigned int)(offset >> 32);
+    sp.logits = sm.logits; sp.ld = sm.ld; sp.vocab = e->cfg.vocab; sp.inv_temperature = 1.0f / sm.temperature;
+    sp.top_k = sm.top_k; sp.top_p = sm.top_p;
+    sp.seed_lo = (unsigned int)sm.seed; sp.seed_hi = (unsigned int)(sm.seed >> 32);
+    sp.off_lo = (unsigned int)sm.offset; sp.off_hi = (unsigned int)(sm.offset >> 32);
     sp.tag0 = tag0; sp.tokens_out = tokens_dev; sp.probs_out = probs;
     sp.embed = e->embed; sp.hidden = e->cfg.hidden; sp.embed_dst = embed_dst;
-    if (sp.vocab <= LSK_SAMPLE_REG_VOCAB || e->samp_hist == nullptr || (ld & 3)) {
+    if (sp.vocab <= LSK_SAMPLE_REG_VOCAB || e->samp_hist == nullptr || (sm.ld & 3)) {
         hipLaunchKernelGGL(lsk_sample_kernel, dim3(m), dim3(LSK_SAMPLE_THREADS), 0, st, sp);
         HIP_OK(hipGetLastError());
         return 0;
@@ -99,6 +99,29 @@ static int launch_sample(lsk_engine* e, const float* logits, int ld, int m, floa
     return sample_sequence_status(e, st);
 }
 
+// Final norm + lm_head over m rows of x, then each row's token into tokens_dev[0..m).  sm == nullptr: the argmax; embed_dst receives the
+// token's embedding row and kv_add > 0 advances the context in the same launch.  Otherwise the head writes logits only (the token is
+// drawn, not maximised) and launch_sample draws with tags tag0.. at sm->offset, leaving the warped distributions in `probs`; a head
+// without an argmax launch cannot advance the context, so kv_add must be 0.
+static int head_token(lsk_engine* e, const elem_t* x, int m, int* tokens_dev, elem_t* embed_dst, int kv_add, hipStream_t st,
+                      const StepSampling* sm, int tag0, float* probs) {
+    if (sm == nullptr) return lsk_run_head_dev(e, x, m, nullptr, 0, tokens_dev, st, embed_dst, kv_add);
+    LSK_TRY(lsk_run_head_dev(e, x, m, sm->logits, sm->ld, nullptr, st, nullptr, kv_add));
+    return launch_sample(e, *sm, m, tag0, tokens_dev, probs, embed_dst, st);
+}
+
+// The prompt from host ids: all rows but the last through layers [0, layer_end), the last id's embedding into hrow[0].
+static int prompt_prefill(lsk_engine* e, const int32_t* input_ids, int P, int layer_end, hipStream_t st) {
+    if (P > 1) HIP_OK(hipMemcpyAsync(e->bulk_ids, input_ids, sizeof(int) * (P - 1), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(e->row_tokens, input_ids + (P - 1), sizeof(int), hipMemcpyHostToDevice, st));
+    e->next_token_host = -1;
+    if (P > 1) {
+        LSK_TRY(lsk_embed_rows_dev(e, e->bulk_ids, P - 1, e->hbulk, st));
+        LSK_TRY(lsk_run_bulk_dev(e, P - 1, &e->state->kv_len, 0, layer_end, st));
+    }
+    return lsk_embed_rows_dev(e, e->row_tokens, 1, e->hrow, st);
+}
+
 // Enqueue every kernel of ONE speculation step plus the copy of its result block into pinned slot `slot`.
 // Nothing here needs the outcome of the previous step on the host: positions come from the device-side
 // kv_len, the input token of a continuing step sits in row_tokens[0] (left there by the previous accept
@@ -120,29 +143,19 @@ static int enqueue_step_body(lsk_engine* e, int P, int S, int E, int n_eos, int 
         elem_t* xr = e->hrow + (size_t)j * c.hidden;
         if (j == 0) LSK_TRY(lsk_embed_rows_dev(e, e->row_tokens, 1, xr, st));   // rows j > 0 were embedded by the previous head
         LSK_TRY(lsk_run_layers_dev(e, xr, 1, kvp, P - 1 + j, 0, E, st));   // j == S: forward_remainder's early pass (LMU:350-362)
-        if (j < S) {
-            if (sm == nullptr) {
-                LSK_TRY(lsk_run_head_dev(e, xr, 1, nullptr, 0, e->row_tokens + j + 1, st, xr + c.hidden));
-            } else {
-                LSK_TRY(lsk_run_head_dev(e, xr, 1, sm->logits, sm->ld, nullptr, st));          // logits only: the token is drawn, not maximised
-                LSK_TRY(launch_sample(e, sm->logits, sm->ld, 1, sm->temperature, sm->top_k, sm->top_p, sm->seed, sm->offset, j,
-                                      e->row_tokens + j + 1, sm->p_draft + (size_t)j * sm->ld, xr + c.hidden, st));
-            }
-        }
+        // draft j + 1 -> row_tokens[j + 1], its embedding -> the next row (sampled: RNG tag j, its distribution -> p_draft row j)
+        if (j < S)
+            LSK_TRY(head_token(e, xr, 1, e->row_tokens + j + 1, xr + c.hidden, 0, st, sm, j, sm ? sm->p_draft + (size_t)j * sm->ld : nullptr));
     }
     // ---- forward_remainder, late layers (LMU:364-383): exit_query_cache rows + last draft row ----
     if (P > 1) LSK_TRY(lsk_run_bulk_dev(e, P - 1, kvp, E, L, st));
     LSK_TRY(lsk_run_layers_dev(e, e->hrow, S + 1, kvp, P - 1, E, L, st));
+    LSK_TRY(head_token(e, e->hrow, S + 1, e->verified, nullptr, 0, st, sm, LSK_TAG_VERIFY, sm ? sm->p_verify : nullptr));
+    // ---- accept + rollback (SSG:186-221) ----
     int* dres = e->result + slot * 64;
     if (sm == nullptr) {
-        LSK_TRY(lsk_run_head_dev(e, e->hrow, S + 1, nullptr, 0, e->verified, st));
-        // ---- accept + rollback (SSG:186-221) ----
         hipLaunchKernelGGL(lsk_accept_kernel, dim3(1), dim3(64), 0, st, e->row_tokens + 1, e->verified, S, e->eos, n_eos, P, e->state, dres);
-        HIP_OK(hipGetLastError());
     } else {
-        LSK_TRY(lsk_run_head_dev(e, e->hrow, S + 1, sm->logits, sm->ld, nullptr, st));
-        LSK_TRY(launch_sample(e, sm->logits, sm->ld, S + 1, sm->temperature, sm->top_k, sm->top_p, sm->seed, sm->offset, LSK_TAG_VERIFY,
-                              e->verified, sm->p_verify, nullptr, st));
         AcceptSampledParams ap{};
         ap.draft = e->row_tokens + 1; ap.verified = e->verified; ap.num_drafts = S; ap.eos = e->eos; ap.n_eos = n_eos; ap.prompt_len = P;
         ap.p_draft = sm->p_draft; ap.p_verify = sm->p_verify; ap.ld = sm->ld; ap.vocab = c.vocab;
@@ -150,8 +163,8 @@ static int enqueue_step_body(lsk_engine* e, int P, int S, int E, int n_eos, int 
         ap.off_lo = (unsigned int)sm->offset; ap.off_hi = (unsigned int)(sm->offset >> 32);
         ap.tag_accept = LSK_TAG_ACCEPT; ap.tag_residual = LSK_TAG_RESIDUAL; ap.st = e->state; ap.result = dres;
         hipLaunchKernelGGL(lsk_accept_sampled_kernel, dim3(1), dim3(LSK_SAMPLE_THREADS), 0, st, ap);
-        HIP_OK(hipGetLastError());
     }
+    HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(e->host_result + slot * 64, dres, sizeof(int) * LSK_RES_INTS, hipMemcpyDeviceToHost, st));
     return 0;
 }
@@ -185,7 +198,7 @@ static int enqueue_step_graph(lsk_engine* e, int S, int E, int n_eos, int slot, 
     return 0;
 }
 
-static int enqueue_step(lsk_engine* e, int P, int S, int E, int n_eos, int slot, hipStream_t st, const StepSampling* sm = nullptr) {
+static int enqueue_step(lsk_engine* e, int P, int S, int E, int n_eos, int slot, hipStream_t st, const StepSampling* sm) {
     if (e->graph_steps && P == 1 && sm == nullptr && !e->profile && st == e->own_stream && e->kv_len_host + 1 + S <= e->cfg.max_ctx) {
         LSK_TRY(enqueue_step_graph(e, S, E, n_eos, slot, st));
     } else {
@@ -206,15 +219,15 @@ static int validate_step_args(lsk_engine* e, int P, int S, int E, const int32_t*
     return 0;
 }
 
-extern "C" int lsk_spec_step(lsk_engine* e, const int32_t* input_ids, int32_t prompt_len, int32_t num_speculations, int32_t exit_layer,
-                             const int32_t* eos_token_ids, int32_t n_eos, lsk_step_result* out, void* stream) {
+// single_step_speculation (SSG:101-229); sm != nullptr: sample=True (decode_next_token llama_model_utils.py:109-131), every argmax
+// replaced by a draw from the warped distribution and the greedy prefix match by modified rejection sampling -- all on the device.
+static int spec_step_impl(lsk_engine* e, const int32_t* input_ids, int P, int S, int exit_layer, const int32_t* eos_token_ids, int n_eos,
+                          lsk_step_result* out, hipStream_t st, const StepSampling* sm) {
     LSK_TRY(lsk_ready(e));
-    hipStream_t st = (hipStream_t)stream;
-    const int P = prompt_len, S = num_speculations;
     if (!input_ids || !out) return lsk_fail("lsk_spec_step: null pointer");
     LSK_TRY(validate_step_args(e, P, S, exit_layer, eos_token_ids, n_eos));
     LSK_TRY(upload_step_inputs(e, input_ids, P, eos_token_ids, n_eos, st));
-    LSK_TRY(enqueue_step(e, P, S, exit_layer, n_eos, 0, st));
+    LSK_TRY(enqueue_step(e, P, S, exit_layer, n_eos, 0, st, sm));
     HIP_OK(hipEventSynchronize(e->step_done[0]));
     const int* host_res = e->host_result;
     memset(out, 0, sizeof(*out));
@@ -229,6 +242,11 @@ extern "C" int lsk_spec_step(lsk_engine* e, const int32_t* input_ids, int32_t pr
     e->next_token_host = host_res[2];
     e->kv_len_host = host_res[3];
     return 0;
+}
+
+extern "C" int lsk_spec_step(lsk_engine* e, const int32_t* input_ids, int32_t prompt_len, int32_t num_speculations, int32_t exit_layer,
+                             const int32_t* eos_token_ids, int32_t n_eos, lsk_step_result* out, void* stream) {
+    return spec_step_impl(e, input_ids, prompt_len, num_speculations, exit_layer, eos_token_ids, n_eos, out, (hipStream_t)stream, nullptr);
 }
 
 // SelfSpeculativeGenerationStrategy.generate_token_ids (self_speculation_generator.py:32-99), greedy, without
@@ -354,73 +372,81 @@ extern "C" int lsk_spec_generate(lsk_engine* e, const int32_t* prompt_ids, int32
                               total_matches, total_drafts, step_drafts, step_matches, n_steps, stream, nullptr);
 }
 
-extern "C" int lsk_ar_step(lsk_engine* e, const int32_t* input_ids, int32_t n_ids, int32_t layer_end, int32_t* next_token, void* stream) {
-    LSK_TRY(lsk_ready(e));
-    hipStream_t st = (hipStream_t)stream;
+// ---- AutoRegressiveGenerationStrategy (autoregressive_generator.py:26-80); sm != nullptr: sample=True (LMU:123-131) -----------------
+// DRAW CONTRACT.  In a sampled autoregressive generation with key `seed` and counter base `offset`, token i is the draw
+// lsk_sample_rows makes over that position's logits row at counter `offset + i` with tag0 = LSK_TAG_VERIFY (row 0 of the
+// draw).  That is exactly the draw step i of lsk_spec_generate_sampled makes with num_speculations = 0: nothing is drafted,
+// the verify block is the one input row at full depth, launch_sample(..., 1 row, LSK_TAG_VERIFY) at offset + i, and the
+// acceptance kernel emits that token unchanged.  So under one (seed, offset) the fused loop, the stepwise form and the layer
+// pipeline's zero-speculation sampled step (lsk_pipeline_tail_sampled) give the same tokens.
+//
+// The sampled head writes a logits row and has no argmax launch to carry the context advance of the greedy loop; the rows
+// therefore sit at pos_off = P - 1 + i over a context length that stays 0 (the same absolute positions: every kernel adds the two),
+// and the final length is set once at the end.
+static int validate_ar_args(lsk_engine* e, const int32_t* input_ids, int32_t n_ids, int32_t layer_end) {
     const lsk_config& c = e->cfg;
-    if (!input_ids || !next_token) return lsk_fail("lsk_ar_step: null pointer");
     if (n_ids < 1 || n_ids - 1 > c.max_prompt) return lsk_fail("n_ids %d out of range", n_ids);
     if (layer_end < 1 || layer_end > c.num_layers) return lsk_fail("layer_end %d out of range", layer_end);
     LSK_TRY(lsk_layers_bound(e, 0, layer_end));
-    if (e->kv_len_host + n_ids > c.max_ctx) return lsk_fail("context overflow");
-    LSK_TRY(lsk_check_ids(e, input_ids, n_ids));
+    return lsk_check_ids(e, input_ids, n_ids);
+}
+
+// One token over the new ids (a streamer or stopping criteria is attached); the context advances by the P new tokens.
+static int ar_step_impl(lsk_engine* e, const int32_t* input_ids, int32_t n_ids, int32_t layer_end, int32_t* next_token, hipStream_t st,
+                        const StepSampling* sm) {
+    LSK_TRY(lsk_ready(e));
+    if (!input_ids || !next_token) return lsk_fail("lsk_ar_step: null pointer");
+    LSK_TRY(validate_ar_args(e, input_ids, n_ids, layer_end));
+    if (e->kv_len_host + n_ids > e->cfg.max_ctx) return lsk_fail("context overflow");
     const int P = n_ids;
-    if (P > 1) HIP_OK(hipMemcpyAsync(e->bulk_ids, input_ids, sizeof(int) * (P - 1), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(e->row_tokens, input_ids + (P - 1), sizeof(int), hipMemcpyHostToDevice, st));
-    e->next_token_host = -1;
-    const int* kvp = &e->state->kv_len;
-    if (P > 1) {
-        LSK_TRY(lsk_embed_rows_dev(e, e->bulk_ids, P - 1, e->hbulk, st));
-        LSK_TRY(lsk_run_bulk_dev(e, P - 1, kvp, 0, layer_end, st));
-    }
-    LSK_TRY(lsk_embed_rows_dev(e, e->row_tokens, 1, e->hrow, st));
-    LSK_TRY(lsk_run_layers_dev(e, e->hrow, 1, kvp, P - 1, 0, layer_end, st));
-    LSK_TRY(lsk_run_head_dev(e, e->hrow, 1, nullptr, 0, e->verified, st, nullptr, P));      // argmax + the context advances by the P new tokens
+    LSK_TRY(prompt_prefill(e, input_ids, P, layer_end, st));
+    LSK_TRY(lsk_run_layers_dev(e, e->hrow, 1, &e->state->kv_len, P - 1, 0, layer_end, st));
+    // greedy: the argmax launch advances the context; sampled: the draw at counter `offset`, then the advance on its own
+    LSK_TRY(head_token(e, e->hrow, 1, e->verified, nullptr, sm ? 0 : P, st, sm, LSK_TAG_VERIFY, sm ? sm->p_verify : nullptr));
+    if (sm) LSK_TRY(lsk_set_kv_len_dev(e, P, true, st));
     HIP_OK(hipMemcpyAsync(next_token, e->verified, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     return 0;
 }
 
-// AutoRegressiveGenerationStrategy.generate_token_ids (autoregressive_generator.py:26-80), greedy, without
-// processors / criteria / streamer, in one call: the argmax of step t is embedded straight into the input row of
-// step t+1 on the device; the host only looks at the produced ids every AR_BLOCK tokens (EOS check, ARG:66-67),
-// so at most AR_BLOCK-1 redundant forward passes run after an EOS (their KV slots lie beyond the final length).
+extern "C" int lsk_ar_step(lsk_engine* e, const int32_t* input_ids, int32_t n_ids, int32_t layer_end, int32_t* next_token, void* stream) {
+    return ar_step_impl(e, input_ids, n_ids, layer_end, next_token, (hipStream_t)stream, nullptr);
+}
+
+// The whole generation without processors / criteria / streamer in one call: token t and its embedding go straight into the input
+// row of token t+1 on the device; the host only looks at the produced ids every AR_BLOCK tokens (EOS check, ARG:66-67), so at most
+// AR_BLOCK-1 redundant forward passes run after an EOS (their KV slots lie beyond the final length).
 #define LSK_AR_BLOCK 8
-extern "C" int lsk_ar_generate(lsk_engine* e, const int32_t* input_ids, int32_t n_ids, int32_t layer_end, const int32_t* eos_token_ids,
-                               int32_t n_eos, int32_t max_steps, int32_t* out_tokens, int32_t* n_out, void* stream) {
+static int ar_generate_impl(lsk_engine* e, const int32_t* input_ids, int32_t n_ids, int32_t layer_end, const int32_t* eos_token_ids,
+                            int32_t n_eos, int32_t max_steps, int32_t* out_tokens, int32_t* n_out, void* stream, const StepSampling* sm) {
     LSK_TRY(lsk_ready(e));
     hipStream_t st = (hipStream_t)stream;
-    const lsk_config& c = e->cfg;
     if (!input_ids || !out_tokens || !n_out) return lsk_fail("lsk_ar_generate: null pointer");
-    if (n_ids < 1 || n_ids - 1 > c.max_prompt) return lsk_fail("n_ids %d out of range", n_ids);
-    if (layer_end < 1 || layer_end > c.num_layers) return lsk_fail("layer_end %d out of range", layer_end);
     if (max_steps < 1) return lsk_fail("max_steps %d < 1", max_steps);
     if (n_eos < 0 || n_eos > LSK_MAX_EOS || (n_eos > 0 && !eos_token_ids)) return lsk_fail("bad eos list");
-    LSK_TRY(lsk_layers_bound(e, 0, layer_end));
-    if (n_ids + max_steps + LSK_AR_BLOCK > c.max_ctx) return lsk_fail("context overflow: %d + %d > max_ctx %d", n_ids, max_steps + LSK_AR_BLOCK, c.max_ctx);
-    LSK_TRY(lsk_check_ids(e, input_ids, n_ids));
+    LSK_TRY(validate_ar_args(e, input_ids, n_ids, layer_end));
+    if (n_ids + max_steps + LSK_AR_BLOCK > e->cfg.max_ctx)
+        return lsk_fail("context overflow: %d + %d > max_ctx %d", n_ids, max_steps + LSK_AR_BLOCK, e->cfg.max_ctx);
+    if (!e->embed) return lsk_fail("lsk_ar_generate: the embedding is not bound on this engine");
     LSK_TRY(lsk_engine_reset(e, stream));
     const int P = n_ids;
-    if (P > 1) HIP_OK(hipMemcpyAsync(e->bulk_ids, input_ids, sizeof(int) * (P - 1), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(e->row_tokens, input_ids + (P - 1), sizeof(int), hipMemcpyHostToDevice, st));
-    e->next_token_host = -1;
+    LSK_TRY(prompt_prefill(e, input_ids, P, layer_end, st));
     const int* kvp = &e->state->kv_len;
-    if (P > 1) {
-        LSK_TRY(lsk_embed_rows_dev(e, e->bulk_ids, P - 1, e->hbulk, st));
-        LSK_TRY(lsk_run_bulk_dev(e, P - 1, kvp, 0, layer_end, st));
-    }
-    LSK_TRY(lsk_embed_rows_dev(e, e->row_tokens, 1, e->hrow, st));
-    int produced = 0, fed = P;          // tokens accepted so far; tokens whose KV the next pass appends after
+    StepSampling tok_sm{};              // sampled: token t is drawn at counter offset + t
+    if (sm) tok_sm = *sm;
+    int produced = 0;                   // tokens emitted so far = tokens made so far while no EOS has come back
     bool done = false;
-    int first = 1;
     while (!done) {
         const int blk = (max_steps - produced) < LSK_AR_BLOCK ? (max_steps - produced) : LSK_AR_BLOCK;
         for (int i = 0; i < blk; ++i) {
-            // the row at hrow[0] is the embedding of the current input token; it sits at position kv_len + (P-1 | 0)
-            LSK_TRY(lsk_run_layers_dev(e, e->hrow, 1, kvp, first ? P - 1 : 0, 0, layer_end, st));
-            // next token -> hrow[0]; the same launch advances the context (the one-thread launch that did only that cost a dispatch per token)
-            LSK_TRY(lsk_run_head_dev(e, e->hrow, 1, nullptr, 0, e->verified + i, st, e->hrow, first ? P : 1));
-            first = 0;
+            // hrow[0] is the embedding of token t's input.  Greedy: it sits at position kv_len + (P-1 | 0) and the argmax launch advances
+            // the context (the one-thread launch that did only that cost a dispatch per token).  Sampled: at P - 1 + t over a context of 0.
+            const int t = produced + i;
+            const int pos_off = sm ? P - 1 + t : (t == 0 ? P - 1 : 0), kv_add = sm ? 0 : (t == 0 ? P : 1);
+            LSK_TRY(lsk_run_layers_dev(e, e->hrow, 1, kvp, pos_off, 0, layer_end, st));
+            if (sm) tok_sm.offset = sm->offset + (uint64_t)t;
+            // token t -> verified[i], its embedding -> hrow[0] (the next input row)
+            LSK_TRY(head_token(e, e->hrow, 1, e->verified + i, e->hrow, kv_add, st, sm ? &tok_sm : nullptr, LSK_TAG_VERIFY, tok_sm.p_verify));
         }
         HIP_OK(hipMemcpyAsync(e->host_result, e->verified, sizeof(int) * blk, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
@@ -428,16 +454,20 @@ extern "C" int lsk_ar_generate(lsk_engine* e, const int32_t* input_ids, int32_t 
             const int tok = e->host_result[i];
             for (int k = 0; k < n_eos; ++k)
                 if (tok == eos_token_ids[k]) done = true;          // EOS is not emitted (ARG:66-67)
-            if (!done) { out_tokens[produced++] = tok; ++fed; }
+            if (!done) out_tokens[produced++] = tok;
         }
         if (produced >= max_steps) done = true;
     }
     // the verified context = prompt + emitted tokens minus the last one (its KV was never needed / is beyond the cut)
     LSK_TRY(lsk_set_kv_len_dev(e, P + (produced > 0 ? produced - 1 : 0), false, st));
     HIP_OK(hipStreamSynchronize(st));
-    (void)fed;
     *n_out = produced;
     return 0;
+}
+
+extern "C" int lsk_ar_generate(lsk_engine* e, const int32_t* input_ids, int32_t n_ids, int32_t layer_end, const int32_t* eos_token_ids,
+                               int32_t n_eos, int32_t max_steps, int32_t* out_tokens, int32_t* n_out, void* stream) {
+    return ar_generate_impl(e, input_ids, n_ids, layer_end, eos_token_ids, n_eos, max_steps, out_tokens, n_out, stream, nullptr);
 }
 
 // ---- layer-range pipeline: the rank-0 half of a step as one asynchronous call -------------------
@@ -459,27 +489,15 @@ static int draft_block_impl(lsk_engine* e, const int32_t* input_ids, int32_t pro
         if (P < 1 || P - 1 > c.max_prompt) return lsk_fail("prompt_len %d out of range (max_prompt %d)", P, c.max_prompt);
         if (row0 != 0 || pos_off0 != P - 1) return lsk_fail("lsk_draft_block: a block that starts from host ids starts at row 0, position P-1");
         LSK_TRY(lsk_check_ids(e, input_ids, P));
-        if (P > 1) HIP_OK(hipMemcpyAsync(e->bulk_ids, input_ids, sizeof(int) * (P - 1), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(e->row_tokens, input_ids + (P - 1), sizeof(int), hipMemcpyHostToDevice, st));
-        e->next_token_host = -1;
-        if (P > 1) {
-            LSK_TRY(lsk_embed_rows_dev(e, e->bulk_ids, P - 1, e->hbulk, st));
-            LSK_TRY(lsk_run_bulk_dev(e, P - 1, kvp, 0, E, st));
-        }
-        LSK_TRY(lsk_embed_rows_dev(e, e->row_tokens, 1, e->hrow, st));
+        LSK_TRY(prompt_prefill(e, input_ids, P, E, st));
     }   // else: row0 was embedded by the head of the previous block (a continuation)
     for (int j = 0; j < n_rows; ++j) {
         elem_t* xr = e->hrow + (size_t)(row0 + j) * c.hidden;
         LSK_TRY(lsk_run_layers_dev(e, xr, 1, kvp, pos_off0 + j, 0, E, st));
         if (!(j + 1 < n_rows || head_last)) continue;
-        if (sm == nullptr) {
-            LSK_TRY(lsk_run_head_dev(e, xr, 1, nullptr, 0, e->row_tokens + row0 + j + 1, st, xr + c.hidden));
-        } else {
-            // draft j of the block is drawn with RNG tag j and leaves its warped distribution in p_draft row (row0 + j), as in enqueue_step_body
-            LSK_TRY(lsk_run_head_dev(e, xr, 1, sm->logits, sm->ld, nullptr, st));
-            LSK_TRY(launch_sample(e, sm->logits, sm->ld, 1, sm->temperature, sm->top_k, sm->top_p, sm->seed, sm->offset, j,
-                                  e->row_tokens + row0 + j + 1, sm->p_draft + (size_t)(row0 + j) * sm->ld, xr + c.hidden, st));
-        }
+        // sampled: draft j of the block is drawn with RNG tag j and leaves its warped distribution in p_draft row (row0 + j), as in enqueue_step_body
+        LSK_TRY(head_token(e, xr, 1, e->row_tokens + row0 + j + 1, xr + c.hidden, 0, st, sm, j,
+                           sm ? sm->p_draft + (size_t)(row0 + j) * sm->ld : nullptr));
     }
     return 0;
 }
@@ -519,15 +537,28 @@ extern "C" int lsk_pipeline_apply(lsk_engine* e, int32_t kv_bound, void* stream)
     return 0;
 }
 
-extern "C" int lsk_pipeline_tail(lsk_engine* e, int32_t m, void* result_dev, void* stream) {
+// Last rank: head + the token of every message row [1, 1 + m) (sampled: the verify draws), then the acceptance kernel
+static int pipeline_tail_impl(lsk_engine* e, int m, int* result, hipStream_t st, const StepSampling* sm) {
     LSK_TRY(lsk_ready(e));
-    if (m < 1 || m > LSK_MAX_ROWS || !result_dev) return lsk_fail("lsk_pipeline_tail: bad arguments");
+    if (m < 1 || m > LSK_MAX_ROWS || !result) return lsk_fail("lsk_pipeline_tail: bad arguments");
     if (e->n_eos_host < 0) return lsk_fail("lsk_pipeline_tail: eos list not set (lsk_engine_set_eos)");
-    hipStream_t st = (hipStream_t)stream;
-    LSK_TRY(lsk_run_head_dev(e, e->hmsg + e->cfg.hidden, m, nullptr, 0, e->verified, st));
-    hipLaunchKernelGGL(lsk_pipeline_accept_kernel, dim3(1), dim3(64), 0, st, e->hmsg, e->verified, e->eos, e->n_eos_host, e->state, (int*)result_dev);
+    LSK_TRY(head_token(e, e->hmsg + e->cfg.hidden, m, e->verified, nullptr, 0, st, sm, LSK_TAG_VERIFY, sm ? sm->p_verify : nullptr));
+    if (sm == nullptr) {
+        hipLaunchKernelGGL(lsk_pipeline_accept_kernel, dim3(1), dim3(64), 0, st, e->hmsg, e->verified, e->eos, e->n_eos_host, e->state, result);
+    } else {
+        PipeAcceptSampledParams ap{};
+        ap.msg = e->hmsg; ap.verified = e->verified; ap.eos = e->eos; ap.n_eos = e->n_eos_host; ap.p_verify = sm->p_verify; ap.ld = sm->ld;
+        ap.seed_lo = (unsigned int)sm->seed; ap.seed_hi = (unsigned int)(sm->seed >> 32);
+        ap.off_lo = (unsigned int)sm->offset; ap.off_hi = (unsigned int)(sm->offset >> 32);
+        ap.tag_accept = LSK_TAG_ACCEPT; ap.st = e->state; ap.result = result;
+        hipLaunchKernelGGL(lsk_pipeline_accept_sampled_kernel, dim3(1), dim3(LSK_SAMPLE_THREADS), 0, st, ap);
+    }
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+extern "C" int lsk_pipeline_tail(lsk_engine* e, int32_t m, void* result_dev, void* stream) {
+    return pipeline_tail_impl(e, m, (int*)result_dev, (hipStream_t)stream, nullptr);
 }
 
 extern "C" int lsk_get_row_tokens(lsk_engine* e, int32_t row0, int32_t n, int32_t* out, void* stream) {
@@ -575,12 +606,15 @@ extern "C" int lsk_sample_rows(lsk_engine* e, const void* logits, int32_t ld, in
     if (!logits || !tokens_out || !probs_out) return lsk_fail("lsk_sample_rows: null pointer");
     if (m < 1 || m > LSK_MAX_ROWS + 1 || ld < e->cfg.vocab) return lsk_fail("lsk_sample_rows: m=%d ld=%d out of range", m, ld);
     LSK_TRY(check_sampling_args(temperature, &top_p));
-    return launch_sample(e, (const float*)logits, ld, m, temperature, top_k, top_p, seed, offset, tag0, tokens_out, (float*)probs_out, nullptr,
-                         (hipStream_t)stream);
+    StepSampling sm{};
+    sm.temperature = temperature; sm.top_k = top_k; sm.top_p = top_p; sm.seed = seed; sm.offset = offset;
+    sm.logits = (float*)logits; sm.ld = ld;
+    return launch_sample(e, sm, m, tag0, tokens_out, (float*)probs_out, nullptr, (hipStream_t)stream);
 }
 
 static int make_step_sampling(lsk_engine* e, float temperature, int32_t top_k, float top_p, uint64_t seed, uint64_t offset, void* scratch,
                               size_t scratch_bytes, StepSampling* sm) {
+    LSK_TRY(lsk_ready(e));
     LSK_TRY(check_sampling_args(temperature, &top_p));
     if (!scratch) return lsk_fail("null sampling scratch");
     size_t need = 0;
@@ -594,36 +628,13 @@ static int make_step_sampling(lsk_engine* e, float temperature, int32_t top_k, f
     return 0;
 }
 
-// single_step_speculation with sample=True (self_speculation_generator.py:101-229, decode_next_token
-// llama_model_utils.py:109-131): the step of lsk_spec_step with every argmax replaced by a draw from the warped
-// distribution and the greedy prefix match replaced by modified rejection sampling -- all on the device.
 extern "C" int lsk_spec_step_sampled(lsk_engine* e, const int32_t* input_ids, int32_t prompt_len, int32_t num_speculations,
                                      int32_t exit_layer, const int32_t* eos_token_ids, int32_t n_eos, float temperature, int32_t top_k,
                                      float top_p, uint64_t seed, uint64_t offset, void* scratch, size_t scratch_bytes,
                                      lsk_step_result* out, void* stream) {
-    LSK_TRY(lsk_ready(e));
-    hipStream_t st = (hipStream_t)stream;
-    const int P = prompt_len, S = num_speculations;
-    if (!input_ids || !out) return lsk_fail("lsk_spec_step_sampled: null pointer");
-    LSK_TRY(validate_step_args(e, P, S, exit_layer, eos_token_ids, n_eos));
     StepSampling sm;
     LSK_TRY(make_step_sampling(e, temperature, top_k, top_p, seed, offset, scratch, scratch_bytes, &sm));
-    LSK_TRY(upload_step_inputs(e, input_ids, P, eos_token_ids, n_eos, st));
-    LSK_TRY(enqueue_step(e, P, S, exit_layer, n_eos, 0, st, &sm));
-    HIP_OK(hipEventSynchronize(e->step_done[0]));
-    const int* host_res = e->host_result;
-    memset(out, 0, sizeof(*out));
-    out->num_matches = host_res[0];
-    out->num_drafts = host_res[1];
-    out->num_emitted = host_res[0] + 1;
-    out->next_token = host_res[2];
-    out->kv_len = host_res[3];
-    for (int i = 0; i <= host_res[0]; ++i) out->emitted[i] = host_res[LSK_RES_EMIT + i];
-    for (int i = 0; i < S; ++i) out->draft_tokens[i] = host_res[LSK_RES_DRAFT + i];
-    for (int i = 0; i <= S; ++i) out->verified_tokens[i] = host_res[LSK_RES_VERIFIED + i];
-    e->next_token_host = host_res[2];
-    e->kv_len_host = host_res[3];
-    return 0;
+    return spec_step_impl(e, input_ids, prompt_len, num_speculations, exit_layer, eos_token_ids, n_eos, out, (hipStream_t)stream, &sm);
 }
 
 // generate_token_ids with sample=True as ONE call: lsk_spec_generate's pipelined loop over sampled steps; step i of the
@@ -634,115 +645,28 @@ extern "C" int lsk_spec_generate_sampled(lsk_engine* e, const int32_t* prompt_id
                                          size_t scratch_bytes, int32_t* out_tokens, int32_t* n_out, int32_t* total_matches,
                                          int32_t* total_drafts, int32_t* step_drafts, int32_t* step_matches, int32_t* n_steps,
                                          void* stream) {
-    LSK_TRY(lsk_ready(e));
     StepSampling sm;
     LSK_TRY(make_step_sampling(e, temperature, top_k, top_p, seed, offset, scratch, scratch_bytes, &sm));
     return spec_generate_impl(e, prompt_ids, prompt_len, num_speculations, exit_layer, eos_token_ids, n_eos, max_steps, out_tokens, n_out,
                               total_matches, total_drafts, step_drafts, step_matches, n_steps, stream, &sm);
 }
 
-// ---- sample=True autoregressive decoding (ARG:26-80 with decode_next_token(sample=True), LMU:123-131) ---------------------
-// DRAW CONTRACT.  In a sampled autoregressive generation with key `seed` and counter base `offset`, token i is the draw
-// lsk_sample_rows makes over that position's logits row at counter `offset + i` with tag0 = LSK_TAG_VERIFY (row 0 of the
-// draw).  That is exactly the draw step i of lsk_spec_generate_sampled makes with num_speculations = 0: nothing is drafted,
-// the verify block is the one input row at full depth, launch_sample(..., 1 row, LSK_TAG_VERIFY) at offset + i, and the
-// acceptance kernel emits that token unchanged.  So under one (seed, offset) the fused loop, the stepwise form and the layer
-// pipeline's zero-speculation sampled step (lsk_pipeline_tail_sampled) give the same tokens.
-//
-// The sampled head writes a logits row and has no argmax launch to carry the context advance of the greedy loop; the rows
-// therefore sit at pos_off = P - 1 + i over a context length that stays 0 (the same absolute positions: every kernel adds the two),
-// and the final length is set once at the end.
-static int ar_sampled_args(lsk_engine* e, const int32_t* input_ids, int32_t n_ids, int32_t layer_end) {
-    const lsk_config& c = e->cfg;
-    if (n_ids < 1 || n_ids - 1 > c.max_prompt) return lsk_fail("n_ids %d out of range", n_ids);
-    if (layer_end < 1 || layer_end > c.num_layers) return lsk_fail("layer_end %d out of range", layer_end);
-    LSK_TRY(lsk_layers_bound(e, 0, layer_end));
-    return lsk_check_ids(e, input_ids, n_ids);
-}
-
-// the prompt (all rows but the last) through layers [0, layer_end) and the last id's embedding into hrow[0]
-static int ar_prefill(lsk_engine* e, const int32_t* input_ids, int P, int layer_end, hipStream_t st) {
-    if (P > 1) HIP_OK(hipMemcpyAsync(e->bulk_ids, input_ids, sizeof(int) * (P - 1), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(e->row_tokens, input_ids + (P - 1), sizeof(int), hipMemcpyHostToDevice, st));
-    e->next_token_host = -1;
-    if (P > 1) {
-        LSK_TRY(lsk_embed_rows_dev(e, e->bulk_ids, P - 1, e->hbulk, st));
-        LSK_TRY(lsk_run_bulk_dev(e, P - 1, &e->state->kv_len, 0, layer_end, st));
-    }
-    return lsk_embed_rows_dev(e, e->row_tokens, 1, e->hrow, st);
-}
-
 extern "C" int lsk_ar_step_sampled(lsk_engine* e, const int32_t* input_ids, int32_t n_ids, int32_t layer_end, float temperature,
                                    int32_t top_k, float top_p, uint64_t seed, uint64_t offset, void* scratch, size_t scratch_bytes,
                                    int32_t* next_token, void* stream) {
-    LSK_TRY(lsk_ready(e));
-    hipStream_t st = (hipStream_t)stream;
-    if (!input_ids || !next_token) return lsk_fail("lsk_ar_step_sampled: null pointer");
-    LSK_TRY(ar_sampled_args(e, input_ids, n_ids, layer_end));
-    if (e->kv_len_host + n_ids > e->cfg.max_ctx) return lsk_fail("context overflow");
     StepSampling sm;
     LSK_TRY(make_step_sampling(e, temperature, top_k, top_p, seed, offset, scratch, scratch_bytes, &sm));
-    const int P = n_ids;
-    LSK_TRY(ar_prefill(e, input_ids, P, layer_end, st));
-    LSK_TRY(lsk_run_layers_dev(e, e->hrow, 1, &e->state->kv_len, P - 1, 0, layer_end, st));
-    LSK_TRY(lsk_run_head_dev(e, e->hrow, 1, sm.logits, sm.ld, nullptr, st));
-    LSK_TRY(launch_sample(e, sm.logits, sm.ld, 1, sm.temperature, sm.top_k, sm.top_p, sm.seed, sm.offset, LSK_TAG_VERIFY, e->verified,
-                          sm.p_verify, nullptr, st));
-    LSK_TRY(lsk_set_kv_len_dev(e, P, true, st));            // the context advances by the P new tokens, as in lsk_ar_step
-    HIP_OK(hipMemcpyAsync(next_token, e->verified, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return 0;
+    return ar_step_impl(e, input_ids, n_ids, layer_end, next_token, (hipStream_t)stream, &sm);
 }
 
-// lsk_ar_generate with every argmax replaced by a draw: the drawn token's embedding goes straight into the input row of the next
-// token on the device; the host looks at the ids once per LSK_AR_BLOCK tokens.  Token i draws at counter offset + i.
+// Token i draws at counter offset + i (the DRAW CONTRACT above ar_step_impl).
 extern "C" int lsk_ar_generate_sampled(lsk_engine* e, const int32_t* input_ids, int32_t n_ids, int32_t layer_end, const int32_t* eos_token_ids,
                                        int32_t n_eos, int32_t max_steps, float temperature, int32_t top_k, float top_p, uint64_t seed,
                                        uint64_t offset, void* scratch, size_t scratch_bytes, int32_t* out_tokens, int32_t* n_out, void* stream) {
-    LSK_TRY(lsk_ready(e));
-    hipStream_t st = (hipStream_t)stream;
-    const lsk_config& c = e->cfg;
-    if (!input_ids || !out_tokens || !n_out) return lsk_fail("lsk_ar_generate_sampled: null pointer");
-    if (max_steps < 1) return lsk_fail("max_steps %d < 1", max_steps);
-    if (n_eos < 0 || n_eos > LSK_MAX_EOS || (n_eos > 0 && !eos_token_ids)) return lsk_fail("bad eos list");
-    LSK_TRY(ar_sampled_args(e, input_ids, n_ids, layer_end));
-    if (n_ids + max_steps + LSK_AR_BLOCK > c.max_ctx) return lsk_fail("context overflow: %d + %d > max_ctx %d", n_ids, max_steps + LSK_AR_BLOCK, c.max_ctx);
-    if (!e->embed) return lsk_fail("lsk_ar_generate_sampled: the embedding is not bound on this engine");
     StepSampling sm;
     LSK_TRY(make_step_sampling(e, temperature, top_k, top_p, seed, offset, scratch, scratch_bytes, &sm));
-    LSK_TRY(lsk_engine_reset(e, stream));
-    const int P = n_ids;
-    LSK_TRY(ar_prefill(e, input_ids, P, layer_end, st));
-    const int* kvp = &e->state->kv_len;
-    int produced = 0;                   // tokens emitted so far = tokens drawn so far while no EOS has come back
-    bool done = false;
-    while (!done) {
-        const int blk = (max_steps - produced) < LSK_AR_BLOCK ? (max_steps - produced) : LSK_AR_BLOCK;
-        for (int i = 0; i < blk; ++i) {
-            const int t = produced + i;     // token index: its input row sits at position P - 1 + t
-            LSK_TRY(lsk_run_layers_dev(e, e->hrow, 1, kvp, P - 1 + t, 0, layer_end, st));
-            LSK_TRY(lsk_run_head_dev(e, e->hrow, 1, sm.logits, sm.ld, nullptr, st));
-            // token t -> verified[i], its embedding -> hrow[0] (the next input row)
-            LSK_TRY(launch_sample(e, sm.logits, sm.ld, 1, sm.temperature, sm.top_k, sm.top_p, sm.seed, sm.offset + (uint64_t)t, LSK_TAG_VERIFY,
-                                  e->verified + i, sm.p_verify, e->hrow, st));
-        }
-        HIP_OK(hipMemcpyAsync(e->host_result, e->verified, sizeof(int) * blk, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        for (int i = 0; i < blk && !done; ++i) {
-            const int tok = e->host_result[i];
-            for (int k = 0; k < n_eos; ++k)
-                if (tok == eos_token_ids[k]) done = true;          // EOS is not emitted (ARG:66-67)
-            if (!done) out_tokens[produced++] = tok;
-        }
-        if (produced >= max_steps) done = true;
-    }
-    // the verified context of lsk_ar_generate: prompt + emitted tokens minus the last one
-    LSK_TRY(lsk_set_kv_len_dev(e, P + (produced > 0 ? produced - 1 : 0), false, st));
-    HIP_OK(hipStreamSynchronize(st));
-    *n_out = produced;
-    return 0;
+    return ar_generate_impl(e, input_ids, n_ids, layer_end, eos_token_ids, n_eos, max_steps, out_tokens, n_out, stream, &sm);
 }
-
 
 // ---- sample=True on the layer pipeline: the sampled step of enqueue_step_body split where its data lives (lsk_sample.h) -------------
 extern "C" int lsk_pipeline_result_words(const lsk_config* cfg, int32_t* out_words) {
@@ -755,7 +679,6 @@ extern "C" int lsk_pipeline_result_words(const lsk_config* cfg, int32_t* out_wor
 extern "C" int lsk_draft_block_sampled(lsk_engine* e, const int32_t* input_ids, int32_t prompt_len, int32_t row0, int32_t n_rows,
                                        int32_t pos_off0, int32_t exit_layer, int32_t head_last, float temperature, int32_t top_k, float top_p,
                                        uint64_t seed, uint64_t offset, void* scratch, size_t scratch_bytes, void* stream) {
-    LSK_TRY(lsk_ready(e));
     StepSampling sm;
     LSK_TRY(make_step_sampling(e, temperature, top_k, top_p, seed, offset, scratch, scratch_bytes, &sm));
     return draft_block_impl(e, input_ids, prompt_len, row0, n_rows, pos_off0, exit_layer, head_last, (hipStream_t)stream, &sm);
@@ -763,7 +686,6 @@ extern "C" int lsk_draft_block_sampled(lsk_engine* e, const int32_t* input_ids, 
 
 extern "C" int lsk_pipeline_pack_sampled(lsk_engine* e, int32_t go, int32_t prompt_len, int32_t src_row, int32_t m, int32_t kv, uint64_t offset,
                                          void* scratch, size_t scratch_bytes, void* stream) {
-    LSK_TRY(lsk_ready(e));
     StepSampling sm;
     LSK_TRY(make_step_sampling(e, 1.0f, 0, 1.0f, 0, offset, scratch, scratch_bytes, &sm));
     return pipeline_pack_impl(e, go, prompt_len, src_row, m, kv, sm.p_draft, sm.ld, offset, (hipStream_t)stream);
@@ -771,29 +693,14 @@ extern "C" int lsk_pipeline_pack_sampled(lsk_engine* e, int32_t go, int32_t prom
 
 extern "C" int lsk_pipeline_tail_sampled(lsk_engine* e, int32_t m, float temperature, int32_t top_k, float top_p, uint64_t seed, uint64_t offset,
                                          void* scratch, size_t scratch_bytes, void* result_dev, int32_t result_words, void* stream) {
-    LSK_TRY(lsk_ready(e));
-    if (m < 1 || m > LSK_MAX_ROWS || !result_dev) return lsk_fail("lsk_pipeline_tail_sampled: bad arguments");
-    if (e->n_eos_host < 0) return lsk_fail("lsk_pipeline_tail_sampled: eos list not set (lsk_engine_set_eos)");
     StepSampling sm;
     LSK_TRY(make_step_sampling(e, temperature, top_k, top_p, seed, offset, scratch, scratch_bytes, &sm));
     if (result_words < LSK_PRES_QROW + sm.ld) return lsk_fail("lsk_pipeline_tail_sampled: result block of %d words, %d needed", result_words, LSK_PRES_QROW + sm.ld);
-    hipStream_t st = (hipStream_t)stream;
-    LSK_TRY(lsk_run_head_dev(e, e->hmsg + e->cfg.hidden, m, sm.logits, sm.ld, nullptr, st));
-    LSK_TRY(launch_sample(e, sm.logits, sm.ld, m, sm.temperature, sm.top_k, sm.top_p, sm.seed, sm.offset, LSK_TAG_VERIFY, e->verified, sm.p_verify,
-                          nullptr, st));
-    PipeAcceptSampledParams ap{};
-    ap.msg = e->hmsg; ap.verified = e->verified; ap.eos = e->eos; ap.n_eos = e->n_eos_host; ap.p_verify = sm.p_verify; ap.ld = sm.ld;
-    ap.seed_lo = (unsigned int)seed; ap.seed_hi = (unsigned int)(seed >> 32);
-    ap.off_lo = (unsigned int)offset; ap.off_hi = (unsigned int)(offset >> 32);
-    ap.tag_accept = LSK_TAG_ACCEPT; ap.st = e->state; ap.result = (int*)result_dev;
-    hipLaunchKernelGGL(lsk_pipeline_accept_sampled_kernel, dim3(1), dim3(LSK_SAMPLE_THREADS), 0, st, ap);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return pipeline_tail_impl(e, m, (int*)result_dev, (hipStream_t)stream, &sm);
 }
 
 extern "C" int lsk_pipeline_residual(lsk_engine* e, void* result_dev, int32_t result_words, int32_t src_row, uint64_t seed, uint64_t offset,
                                      void* scratch, size_t scratch_bytes, void* stream) {
-    LSK_TRY(lsk_ready(e));
     if (!result_dev || src_row < 0 || src_row >= LSK_MAX_ROWS) return lsk_fail("lsk_pipeline_residual: bad arguments");
     StepSampling sm;
     LSK_TRY(make_step_sampling(e, 1.0f, 0, 1.0f, seed, offset, scratch, scratch_bytes, &sm));

@@ -47,6 +47,18 @@ def _i32_array(values: Sequence[int]):
     return arr
 
 
+def _u64(v: int) -> int:
+    """A Philox key / counter as the uint64_t the C ABI takes."""
+    return int(v) & (2 ** 64 - 1)
+
+
+def _host_ids(input_ids: Optional[Sequence[int]]):
+    """(ids array, count) of optional host ids: None = a block that continues on the device (NULL, 1)."""
+    if input_ids is None:
+        return None, 1
+    return _i32_array(input_ids), len(input_ids)
+
+
 class HipEngine:
     """One engine per (model, device).  Not re-entrant; one caller thread (like the reference)."""
 
@@ -335,31 +347,50 @@ class HipEngine:
         self._block_table = [int(t) for t in table]
 
     # ------------------------------------------------------------------ fused fast paths
-    def spec_step(self, input_ids: Sequence[int], num_speculations: int, exit_layer: int,
-                  eos_token_ids: Sequence[int]) -> StepResult:
-        ids = _i32_array(input_ids)
+    # (each greedy / sampled pair shares one body: `fn` is its C function, `sampling` the sampled form's extra arguments)
+    def _spec_step(self, fn, input_ids, num_speculations, exit_layer, eos_token_ids, sampling=()) -> StepResult:
         eos, eos_arr = self._eos_array(eos_token_ids)
         res = LskStepResult()
-        self._ck(self.lib.lsk_spec_step(self._handle, ids, len(input_ids), int(num_speculations), int(exit_layer),
-                                     eos_arr, len(eos), ctypes.byref(res), self._stream))
+        self._ck(fn(self._handle, _i32_array(input_ids), len(input_ids), int(num_speculations), int(exit_layer), eos_arr, len(eos),
+                    *sampling, ctypes.byref(res), self._stream))
         n, s = res.num_matches, int(num_speculations)
         return StepResult(n, res.num_drafts, res.next_token, res.kv_len, list(res.emitted[: n + 1]),
                           list(res.draft_tokens[:s]), list(res.verified_tokens[: s + 1]))
 
-    def spec_generate(self, prompt_ids: Sequence[int], num_speculations: int, exit_layer: int,
-                      eos_token_ids: Sequence[int], max_steps: int):
-        """Whole greedy generation in one C-ABI call.  Returns (tokens, matches, drafts, [(T_d, n) per step])."""
-        ids = _i32_array(prompt_ids)
+    def _spec_generate(self, fn, prompt_ids, num_speculations, exit_layer, eos_token_ids, max_steps, sampling=()):
         eos, eos_arr = self._eos_array(eos_token_ids)
         out = (ctypes.c_int32 * max_steps)()
         sd = (ctypes.c_int32 * max_steps)()
         sm = (ctypes.c_int32 * max_steps)()
         n_out, tm, td, ns = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
-        self._ck(self.lib.lsk_spec_generate(self._handle, ids, len(prompt_ids), int(num_speculations), int(exit_layer), eos_arr,
-                                         len(eos), int(max_steps), out, ctypes.byref(n_out), ctypes.byref(tm), ctypes.byref(td),
-                                         sd, sm, ctypes.byref(ns), self._stream))
+        self._ck(fn(self._handle, _i32_array(prompt_ids), len(prompt_ids), int(num_speculations), int(exit_layer), eos_arr, len(eos),
+                    int(max_steps), *sampling, out, ctypes.byref(n_out), ctypes.byref(tm), ctypes.byref(td), sd, sm, ctypes.byref(ns),
+                    self._stream))
         steps = [(sd[i], sm[i]) for i in range(ns.value)]
         return list(out[: n_out.value]), tm.value, td.value, steps
+
+    def _ar_generate(self, fn, input_ids, layer_end, eos_token_ids, max_steps, sampling=()) -> List[int]:
+        eos, eos_arr = self._eos_array(eos_token_ids)
+        out = (ctypes.c_int32 * max_steps)()
+        n_out = ctypes.c_int32(0)
+        self._ck(fn(self._handle, _i32_array(input_ids), len(input_ids), int(layer_end or self.num_layers), eos_arr, len(eos),
+                    int(max_steps), *sampling, out, ctypes.byref(n_out), self._stream))
+        return list(out[: n_out.value])
+
+    def _ar_step(self, fn, input_ids, layer_end, sampling=()) -> int:
+        tok = ctypes.c_int32(0)
+        self._ck(fn(self._handle, _i32_array(input_ids), len(input_ids), int(layer_end or self.num_layers), *sampling,
+                    ctypes.byref(tok), self._stream))
+        return tok.value
+
+    def spec_step(self, input_ids: Sequence[int], num_speculations: int, exit_layer: int,
+                  eos_token_ids: Sequence[int]) -> StepResult:
+        return self._spec_step(self.lib.lsk_spec_step, input_ids, num_speculations, exit_layer, eos_token_ids)
+
+    def spec_generate(self, prompt_ids: Sequence[int], num_speculations: int, exit_layer: int,
+                      eos_token_ids: Sequence[int], max_steps: int):
+        """Whole greedy generation in one C-ABI call.  Returns (tokens, matches, drafts, [(T_d, n) per step])."""
+        return self._spec_generate(self.lib.lsk_spec_generate, prompt_ids, num_speculations, exit_layer, eos_token_ids, max_steps)
 
     # ------------------------------------------------------------------ sampling on the device (opt-in, SURVEY 8f N2)
     def _sampling_scratch(self) -> torch.Tensor:
@@ -371,6 +402,11 @@ class HipEngine:
             self._buffers["sampling"] = buf
         return buf
 
+    def _sampling_args(self, temperature, top_k, top_p, seed, offset) -> tuple:
+        """The sample=True arguments of a sampled entry point: warping, Philox key and counter, the sampling scratch."""
+        scratch = self._sampling_scratch()
+        return (float(temperature), int(top_k), float(top_p), _u64(seed), _u64(offset), scratch.data_ptr(), scratch.numel())
+
     def sample_rows(self, logits: torch.Tensor, temperature: float, top_k: int, top_p: float, seed: int, offset: int,
                     tag0: int = 0):
         """decode_next_token(sample=True) over rows of device logits [m, ld] (fp32).  Returns (tokens int32[m] on
@@ -381,98 +417,49 @@ class HipEngine:
         toks = torch.empty(m, dtype=torch.int32, device=self.device)
         probs = torch.empty(m, ld, dtype=torch.float32, device=self.device)
         self._ck(self.lib.lsk_sample_rows(self._handle, logits.data_ptr(), ld, m, float(temperature), int(top_k), float(top_p),
-                                       int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(tag0), toks.data_ptr(),
-                                       probs.data_ptr(), self._stream))
+                                       _u64(seed), _u64(offset), int(tag0), toks.data_ptr(), probs.data_ptr(), self._stream))
         return toks, probs
 
     def spec_step_sampled(self, input_ids: Sequence[int], num_speculations: int, exit_layer: int,
                           eos_token_ids: Sequence[int], temperature: float, top_k: int, top_p: float, seed: int,
                           offset: int) -> StepResult:
         """single_step_speculation with sample=True, entirely on the device (lsk_spec_step_sampled)."""
-        ids = _i32_array(input_ids)
-        eos, eos_arr = self._eos_array(eos_token_ids)
-        res = LskStepResult()
-        scratch = self._sampling_scratch()
-        self._ck(self.lib.lsk_spec_step_sampled(self._handle, ids, len(input_ids), int(num_speculations), int(exit_layer), eos_arr,
-                                             len(eos), float(temperature), int(top_k), float(top_p), int(seed) & (2 ** 64 - 1),
-                                             int(offset) & (2 ** 64 - 1), scratch.data_ptr(), scratch.numel(), ctypes.byref(res),
-                                             self._stream))
-        n, s = res.num_matches, int(num_speculations)
-        return StepResult(n, res.num_drafts, res.next_token, res.kv_len, list(res.emitted[: n + 1]),
-                          list(res.draft_tokens[:s]), list(res.verified_tokens[: s + 1]))
+        return self._spec_step(self.lib.lsk_spec_step_sampled, input_ids, num_speculations, exit_layer, eos_token_ids,
+                               self._sampling_args(temperature, top_k, top_p, seed, offset))
 
     def spec_generate_sampled(self, prompt_ids: Sequence[int], num_speculations: int, exit_layer: int,
                               eos_token_ids: Sequence[int], max_steps: int, temperature: float, top_k: int, top_p: float,
                               seed: int, offset: int):
         """Whole sample=True generation in one C-ABI call (lsk_spec_generate_sampled).  Same return as spec_generate."""
-        ids = _i32_array(prompt_ids)
-        eos, eos_arr = self._eos_array(eos_token_ids)
-        out = (ctypes.c_int32 * max_steps)()
-        sd = (ctypes.c_int32 * max_steps)()
-        sm = (ctypes.c_int32 * max_steps)()
-        n_out, tm, td, ns = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
-        scratch = self._sampling_scratch()
-        self._ck(self.lib.lsk_spec_generate_sampled(
-            self._handle, ids, len(prompt_ids), int(num_speculations), int(exit_layer), eos_arr, len(eos), int(max_steps),
-            float(temperature), int(top_k), float(top_p), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
-            scratch.data_ptr(), scratch.numel(), out, ctypes.byref(n_out), ctypes.byref(tm), ctypes.byref(td), sd, sm,
-            ctypes.byref(ns), self._stream))
-        steps = [(sd[i], sm[i]) for i in range(ns.value)]
-        return list(out[: n_out.value]), tm.value, td.value, steps
+        return self._spec_generate(self.lib.lsk_spec_generate_sampled, prompt_ids, num_speculations, exit_layer, eos_token_ids, max_steps,
+                                   self._sampling_args(temperature, top_k, top_p, seed, offset))
 
     def ar_generate(self, input_ids: Sequence[int], layer_end: Optional[int], eos_token_ids: Sequence[int],
                     max_steps: int) -> List[int]:
         """Whole greedy autoregressive generation in one C-ABI call."""
-        ids = _i32_array(input_ids)
-        eos, eos_arr = self._eos_array(eos_token_ids)
-        out = (ctypes.c_int32 * max_steps)()
-        n_out = ctypes.c_int32(0)
-        self._ck(self.lib.lsk_ar_generate(self._handle, ids, len(input_ids), int(layer_end or self.num_layers), eos_arr,
-                                       len(eos), int(max_steps), out, ctypes.byref(n_out), self._stream))
-        return list(out[: n_out.value])
+        return self._ar_generate(self.lib.lsk_ar_generate, input_ids, layer_end, eos_token_ids, max_steps)
 
     def ar_step(self, input_ids: Sequence[int], layer_end: Optional[int] = None) -> int:
-        ids = _i32_array(input_ids)
-        tok = ctypes.c_int32(0)
-        self._ck(self.lib.lsk_ar_step(self._handle, ids, len(input_ids), int(layer_end or self.num_layers),
-                                   ctypes.byref(tok), self._stream))
-        return tok.value
+        return self._ar_step(self.lib.lsk_ar_step, input_ids, layer_end)
 
     def ar_generate_sampled(self, input_ids: Sequence[int], layer_end: Optional[int], eos_token_ids: Sequence[int], max_steps: int,
                             temperature: float, top_k: int, top_p: float, seed: int, offset: int) -> List[int]:
         """Whole sample=True autoregressive generation in one C-ABI call (lsk_ar_generate_sampled): token i draws at Philox
         counter offset + i, the draw step i of spec_generate_sampled makes with num_speculations = 0."""
-        ids = _i32_array(input_ids)
-        eos, eos_arr = self._eos_array(eos_token_ids)
-        out = (ctypes.c_int32 * max_steps)()
-        n_out = ctypes.c_int32(0)
-        scratch = self._sampling_scratch()
-        self._ck(self.lib.lsk_ar_generate_sampled(
-            self._handle, ids, len(input_ids), int(layer_end or self.num_layers), eos_arr, len(eos), int(max_steps), float(temperature),
-            int(top_k), float(top_p), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), scratch.data_ptr(), scratch.numel(), out,
-            ctypes.byref(n_out), self._stream))
-        return list(out[: n_out.value])
+        return self._ar_generate(self.lib.lsk_ar_generate_sampled, input_ids, layer_end, eos_token_ids, max_steps,
+                                 self._sampling_args(temperature, top_k, top_p, seed, offset))
 
     def ar_step_sampled(self, input_ids: Sequence[int], layer_end: Optional[int], temperature: float, top_k: int, top_p: float,
                         seed: int, offset: int) -> int:
         """One sample=True autoregressive token (lsk_ar_step_sampled), drawn at Philox counter `offset`; only the id comes back."""
-        ids = _i32_array(input_ids)
-        tok = ctypes.c_int32(0)
-        scratch = self._sampling_scratch()
-        self._ck(self.lib.lsk_ar_step_sampled(self._handle, ids, len(input_ids), int(layer_end or self.num_layers), float(temperature),
-                                           int(top_k), float(top_p), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
-                                           scratch.data_ptr(), scratch.numel(), ctypes.byref(tok), self._stream))
-        return tok.value
+        return self._ar_step(self.lib.lsk_ar_step_sampled, input_ids, layer_end,
+                             self._sampling_args(temperature, top_k, top_p, seed, offset))
 
     # ------------------------------------------------------------------ layer-range pipeline (rank-0 half of a step)
     def draft_block(self, input_ids: Optional[Sequence[int]], row0: int, n_rows: int, pos_off0: int, exit_layer: int,
                     head_last: bool = False) -> None:
         """Asynchronous device-resident draft loop over step rows [row0, row0 + n_rows) (lsk_draft_block)."""
-        if input_ids is None:
-            ids, n = None, 1
-        else:
-            ids, n = _i32_array(input_ids), len(input_ids)
-        self._ck(self.lib.lsk_draft_block(self._handle, ids, n, int(row0), int(n_rows), int(pos_off0), int(exit_layer),
+        self._ck(self.lib.lsk_draft_block(self._handle, *_host_ids(input_ids), int(row0), int(n_rows), int(pos_off0), int(exit_layer),
                                        1 if head_last else 0, self._stream))
 
     def set_eos(self, eos_token_ids: Sequence[int]) -> None:
@@ -508,21 +495,15 @@ class HipEngine:
                             head_last: bool, temperature: float, top_k: int, top_p: float, seed: int, offset: int) -> None:
         """`draft_block` with every argmax replaced by a draw (draft j of the block: Philox tag j at `offset`); the warped draft
         distributions stay in the sampling scratch (rows row0 + j) for `pipeline_pack_sampled` / `pipeline_residual`."""
-        if input_ids is None:
-            ids, n = None, 1
-        else:
-            ids, n = _i32_array(input_ids), len(input_ids)
-        scratch = self._sampling_scratch()
-        self._ck(self.lib.lsk_draft_block_sampled(self._handle, ids, n, int(row0), int(n_rows), int(pos_off0), int(exit_layer),
-                                               1 if head_last else 0, float(temperature), int(top_k), float(top_p),
-                                               int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), scratch.data_ptr(), scratch.numel(),
-                                               self._stream))
+        self._ck(self.lib.lsk_draft_block_sampled(self._handle, *_host_ids(input_ids), int(row0), int(n_rows), int(pos_off0),
+                                               int(exit_layer), 1 if head_last else 0,
+                                               *self._sampling_args(temperature, top_k, top_p, seed, offset), self._stream))
 
     def pipeline_pack_sampled(self, go: int, prompt_len: int, src_row: int, m: int, kv: int, offset: int) -> None:
         """`pipeline_pack` + the sampled step's header words: mode, Philox offset, p_i(x_i) of every draft."""
         scratch = self._sampling_scratch()
-        self._ck(self.lib.lsk_pipeline_pack_sampled(self._handle, int(go), int(prompt_len), int(src_row), int(m), int(kv),
-                                                 int(offset) & (2 ** 64 - 1), scratch.data_ptr(), scratch.numel(), self._stream))
+        self._ck(self.lib.lsk_pipeline_pack_sampled(self._handle, int(go), int(prompt_len), int(src_row), int(m), int(kv), _u64(offset),
+                                                 scratch.data_ptr(), scratch.numel(), self._stream))
 
     def pipeline_tail_sampled(self, m: int, temperature: float, top_k: int, top_p: float, seed: int, offset: int) -> torch.Tensor:
         """Last rank, sample=True: head + verify draws + the acceptance test against the header's p_i(x_i) -> device int32
@@ -532,9 +513,7 @@ class HipEngine:
         if res is None or res.numel() != words:
             res = torch.zeros(words, dtype=torch.int32, device=self.device)
             self._buffers["pp_result_sampled"] = res
-        scratch = self._sampling_scratch()
-        self._ck(self.lib.lsk_pipeline_tail_sampled(self._handle, int(m), float(temperature), int(top_k), float(top_p),
-                                                 int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), scratch.data_ptr(), scratch.numel(),
+        self._ck(self.lib.lsk_pipeline_tail_sampled(self._handle, int(m), *self._sampling_args(temperature, top_k, top_p, seed, offset),
                                                  res.data_ptr(), words, self._stream))
         return res
 
@@ -544,8 +523,8 @@ class HipEngine:
         if block.dtype != torch.int32 or block.device != self.device or not block.is_contiguous():
             raise _lib.LskError("the result block must be a contiguous int32 tensor on the engine device")
         scratch = self._sampling_scratch()
-        self._ck(self.lib.lsk_pipeline_residual(self._handle, block.data_ptr(), block.numel(), int(src_row), int(seed) & (2 ** 64 - 1),
-                                             int(offset) & (2 ** 64 - 1), scratch.data_ptr(), scratch.numel(), self._stream))
+        self._ck(self.lib.lsk_pipeline_residual(self._handle, block.data_ptr(), block.numel(), int(src_row), _u64(seed), _u64(offset),
+                                             scratch.data_ptr(), scratch.numel(), self._stream))
 
     def logits_rows(self, blocks: Sequence[Sequence[int]]) -> torch.Tensor:
         """Final norm + lm_head logits of the listed (buffer, row_base, count) blocks -> [rows, vocab] in the model dtype (the values

@@ -79,6 +79,19 @@ def decode_rows(logits: torch.Tensor, last_only: bool, sample: bool, temperature
     return tok, probs
 
 
+def _logits_rows(engine: HipEngine, rows: Sequence[Tuple[int, int, int]]) -> torch.Tensor:
+    """Final-norm + lm_head logits of the listed (buffer, row_base, count) blocks -> [1, M, V] (fp32 cast to the engine dtype)."""
+    total = sum(c for _, _, c in rows)
+    out = torch.empty(total, engine.vocab, dtype=torch.float32, device=engine.device)
+    at = 0
+    for buf, base, count in rows:
+        for r0 in range(0, count, _lib.LSK_MAX_ROWS):
+            m = min(_lib.LSK_MAX_ROWS, count - r0)
+            engine.run_head(buf, base + r0, m, logits=out[at:at + m], want_tokens=False)
+            at += m
+    return out.to(getattr(engine, "dtype", torch.bfloat16)).unsqueeze(0)
+
+
 def _residual_distribution(p_verify: torch.Tensor, p_draft: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
     d = torch.clamp(p_verify - p_draft, min=0)
     return d / (d.sum() + eps)
@@ -115,7 +128,7 @@ class HipSelfSpeculativeGenerationStrategy(GenerationStrategy):
             engine.run_bulk(P - 1, E, L)
         engine.run_layers_chunked(sbuf, sbase, td + 1, P - 1, E, L)
         blocks = ([(BUF_BULK, 0, P - 1)] if (P > 1 and prompt_rows) else []) + [(sbuf, sbase, td + 1)]
-        return self._logits_rows(engine, blocks)
+        return _logits_rows(engine, blocks)
 
     def _commit(self, engine: HipEngine, kv_len: int) -> None:
         """crop_past_key_values (SSG:219-221): the verified context length after a step."""
@@ -250,18 +263,6 @@ class HipSelfSpeculativeGenerationStrategy(GenerationStrategy):
         return next_input, output_ids, EngineCache(engine), n, step.num_drafts
 
     # ------------------------------------------------------------------------------ slow path
-    def _logits_rows(self, engine: HipEngine, rows: Sequence[Tuple[int, int, int]], dtype=None) -> torch.Tensor:
-        """Final-norm + lm_head logits of the listed (buffer, row_base, count) blocks -> [1, M, V]."""
-        total = sum(c for _, _, c in rows)
-        out = torch.empty(total, engine.vocab, dtype=torch.float32, device=engine.device)
-        at = 0
-        for buf, base, count in rows:
-            for r0 in range(0, count, _lib.LSK_MAX_ROWS):
-                m = min(_lib.LSK_MAX_ROWS, count - r0)
-                engine.run_head(buf, base + r0, m, logits=out[at:at + m], want_tokens=False)
-                at += m
-        return out.to(dtype or getattr(engine, "dtype", torch.bfloat16)).unsqueeze(0)
-
     def _slow_step(self, engine: HipEngine, ids: List[int], spec: int, exit_layer: int, eos: List[int], sample: bool,
                    temperature: float, top_k: int, top_p: float, processors):
         from .engine import StepResult
@@ -291,7 +292,7 @@ class HipSelfSpeculativeGenerationStrategy(GenerationStrategy):
                 break
             # forward_early returns logits for every input row (LMU:271-273): the prompt rows on call 0
             blocks = ([(BUF_BULK, 0, P - 1)] if (j == 0 and P > 1 and processors) else []) + [(SBUF, SBASE + j, 1)]
-            logits = self._logits_rows(engine, blocks)
+            logits = _logits_rows(engine, blocks)
             if processors:
                 logits = processors(draft_input, logits)
             t, prob = decode_rows(logits, True, sample, temperature, top_k, top_p)
@@ -354,7 +355,7 @@ class HipAutoRegressiveGenerationStrategy(GenerationStrategy):
         engine.embed_rows(ids[-1:], BUF_STEP, 0)
         engine.run_layers(BUF_STEP, 0, 1, P - 1, 0, layer_end)
         blocks = ([(BUF_BULK, 0, P - 1)] if (P > 1 and prompt_rows) else []) + [(BUF_STEP, 0, 1)]
-        return HipSelfSpeculativeGenerationStrategy._logits_rows(None, engine, blocks)
+        return _logits_rows(engine, blocks)
 
     def _commit(self, engine: HipEngine, kv_len: int) -> None:
         engine.set_kv_len(kv_len)
