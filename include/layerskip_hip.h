@@ -82,7 +82,10 @@ typedef struct lsk_step_result {
 const char* lsk_last_error(void);
 int lsk_abi_version(void);
 /* Model dtype this build of the library computes in: 0 = bf16 (liblayerskip_hip.so), 1 = fp16
- * (liblayerskip_hip_f16.so, same sources with -DLSK_ELEM_F16; the dtype generate.py:63 hard-codes). */
+ * (liblayerskip_hip_f16.so, same sources with -DLSK_ELEM_F16; the dtype generate.py:63 hard-codes), 2 = fp32
+ * (liblayerskip_hip_f32.so, same sources with -DLSK_ELEM_F32; HF's default dtype).  Every entry point exists in all three; the
+ * fp32 library's sampled entry points compute with 16-bit logit keys, which are exact at bf16 / fp16 only, so its host (the Python
+ * package) runs sample=True on the host instead. */
 int lsk_elem_dtype(void);
 
 /* ---- sizes ---------------------------------------------------------------------------- */

@@ -18,7 +18,7 @@ extern "C" {
 
 const char* lsk_test_last_error(void);
 int lsk_test_abi_version(void);       /* LSK_ABI_VERSION of the sources it was built from */
-int lsk_test_elem_dtype(void);        /* 0 = bf16, 1 = fp16 (-DLSK_ELEM_F16) */
+int lsk_test_elem_dtype(void);        /* 0 = bf16, 1 = fp16 (-DLSK_ELEM_F16), 2 = fp32 (-DLSK_ELEM_F32: liblayerskip_hip_test_f32.so) */
 
 /* the rejection-sampling kernel alone (tests): all pointers DEVICE; draft[-1] must be addressable; result int32[64] */
 int lsk_test_accept_sampled(int32_t* draft, int32_t* verified, int32_t num_drafts, const int32_t* eos, int32_t n_eos,

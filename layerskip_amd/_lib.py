@@ -22,7 +22,9 @@ LSK_OPT_GRAPH_STEPS = 7       # steady-state greedy steps replayed from hipGraph
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(_CSRC, "liblayerskip_hip.so")            # bf16 build (BASELINE configs)
 LIB_PATH_F16 = os.path.join(_CSRC, "liblayerskip_hip_f16.so")    # fp16 build (same sources, -DLSK_ELEM_F16)
-DTYPE_CODES = {"bf16": 0, "fp16": 1}
+LIB_PATH_F32 = os.path.join(_CSRC, "liblayerskip_hip_f32.so")    # fp32 build (same sources, -DLSK_ELEM_F32)
+DTYPE_CODES = {"bf16": 0, "fp16": 1, "fp32": 2}
+_LIB_PATHS = {"bf16": LIB_PATH, "fp16": LIB_PATH_F16, "fp32": LIB_PATH_F32}
 
 
 class LskConfig(ctypes.Structure):
@@ -121,11 +123,11 @@ class LskError(RuntimeError):
 def load(path: str | None = None, dtype: str = "bf16") -> ctypes.CDLL:
     """Load the HIP extension for a model dtype (once) and type every exported symbol.  Raises if anything is missing."""
     if dtype not in DTYPE_CODES:
-        raise LskError(f"unsupported model dtype {dtype!r} (bf16 or fp16)")
+        raise LskError(f"unsupported model dtype {dtype!r} (bf16, fp16 or fp32)")
     if path is None and dtype in _LIBS:
         return _LIBS[dtype]
     explicit = path is not None
-    path = path or (LIB_PATH if dtype == "bf16" else LIB_PATH_F16)
+    path = path or _LIB_PATHS[dtype]
     import torch  # noqa: F401  -- loads the ROCm runtime (libamdhip64.so.7) the extension links against
     if not os.path.exists(path):
         raise LskError(

@@ -12,9 +12,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "liblayerskip_hip.so")              # bf16: the BASELINE configs
 LIB_F16 = os.path.join(CSRC, "liblayerskip_hip_f16.so")      # fp16: same sources, -DLSK_ELEM_F16 (generate.py:63's dtype)
+LIB_F32 = os.path.join(CSRC, "liblayerskip_hip_f32.so")      # fp32: same sources, -DLSK_ELEM_F32 (HF's default dtype)
 # test infrastructure: single kernels on caller-owned buffers (include/layerskip_hip_test.h); never loaded by the package
 LIB_TEST = os.path.join(CSRC, "liblayerskip_hip_test.so")
 LIB_TEST_F16 = os.path.join(CSRC, "liblayerskip_hip_test_f16.so")
+LIB_TEST_F32 = os.path.join(CSRC, "liblayerskip_hip_test_f32.so")
 SOURCES = ["lsk_engine.hip", "lsk_generate.hip"]             # the product library: two translation units
 TEST_SOURCES = ["lsk_test_exports.hip"]
 
@@ -54,12 +56,12 @@ def _compile(lib: str, defines, verbose: bool, sources=None) -> None:
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    """Builds the product libraries (bf16, fp16) and the test libraries in-tree (when stale); returns the bf16 product one."""
-    jobs = ((LIB, [], SOURCES), (LIB_F16, ["-DLSK_ELEM_F16"], SOURCES),
-            (LIB_TEST, [], TEST_SOURCES), (LIB_TEST_F16, ["-DLSK_ELEM_F16"], TEST_SOURCES))
+    """Builds the product libraries (bf16, fp16, fp32) and the test libraries in-tree (when stale); returns the bf16 product one."""
+    jobs = ((LIB, [], SOURCES), (LIB_F16, ["-DLSK_ELEM_F16"], SOURCES), (LIB_F32, ["-DLSK_ELEM_F32"], SOURCES),
+            (LIB_TEST, [], TEST_SOURCES), (LIB_TEST_F16, ["-DLSK_ELEM_F16"], TEST_SOURCES), (LIB_TEST_F32, ["-DLSK_ELEM_F32"], TEST_SOURCES))
     stale = [j for j in jobs if force or _stale(j[0])]
     if len(stale) > 1:
-        from concurrent.futures import ThreadPoolExecutor      # hipcc is a subprocess: the four builds run side by side
+        from concurrent.futures import ThreadPoolExecutor      # hipcc is a subprocess: the builds run side by side
         with ThreadPoolExecutor(max_workers=len(stale)) as pool:
             list(pool.map(lambda j: _compile(j[0], j[1], verbose, j[2]), stale))
     else:

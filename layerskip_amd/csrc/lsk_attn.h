@@ -203,9 +203,13 @@ __device__ __forceinline__ void lsk_attn_combine_wide(const float* __restrict__ 
 #pragma unroll
         for (int j = 0; j < W / 4; ++j) {
             const elem_t o0 = f2e(a[4 * j] / l), o1 = f2e(a[4 * j + 1] / l), o2 = f2e(a[4 * j + 2] / l), o3 = f2e(a[4 * j + 3] / l);
+#if LSK_EB == 2
             const unsigned long long packed = (unsigned long long)__builtin_bit_cast(unsigned short, o0) | ((unsigned long long)__builtin_bit_cast(unsigned short, o1) << 16) |
                                               ((unsigned long long)__builtin_bit_cast(unsigned short, o2) << 32) | ((unsigned long long)__builtin_bit_cast(unsigned short, o3) << 48);
             *(unsigned long long*)(out + (size_t)r * ldo + head * HD + d + 4 * j) = packed;
+#else
+            *(f32x4*)(out + (size_t)r * ldo + head * HD + d + 4 * j) = (f32x4){o0, o1, o2, o3};     // fp32: one 16-byte store
+#endif
         }
     }
 }
@@ -435,8 +439,13 @@ __device__ __forceinline__ void lsk_attn_body(const AttnHot& hp, const AttnSplit
                 }
             }
             const elem_t o0 = f2e(a0 / l), o1 = f2e(a1 / l);
+#if LSK_EB == 2
             const unsigned packed = (unsigned)__builtin_bit_cast(unsigned short, o0) | ((unsigned)__builtin_bit_cast(unsigned short, o1) << 16);
             *(unsigned*)(p.out + (size_t)r * p.ldo + head * HD + d) = packed;
+#else
+            typedef float f32x2 __attribute__((ext_vector_type(2)));
+            *(f32x2*)(p.out + (size_t)r * p.ldo + head * HD + d) = (f32x2){o0, o1};                 // fp32: one 8-byte store
+#endif
         }
     } else if (n_rows * (HD / 4) <= LSK_ATTN_THREADS) {
         lsk_attn_combine_wide<HD, 4>(p.part, p.out, p.ldo, n_rows, M, inv_m, head0, p.max_pages, base_pos, tid);

@@ -5,24 +5,47 @@
 #include <stdint.h>
 
 // The model dtype is a BUILD-time choice: the same sources give liblayerskip_hip.so (bf16, the BASELINE configs) and,
-// with -DLSK_ELEM_F16, liblayerskip_hip_f16.so (fp16, the dtype the reference's generate.py hard-codes, generate.py:63).
+// with -DLSK_ELEM_F16, liblayerskip_hip_f16.so (fp16, the dtype the reference's generate.py hard-codes, generate.py:63) and, with
+// -DLSK_ELEM_F32, liblayerskip_hip_f32.so (fp32, the dtype HF loads by default and the reference's unit tests use).
 // Everything below is written against elem_t: storage, the rounding points (f2e / rnd_e) and the MFMA instruction.
-#ifdef LSK_ELEM_F16
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#if defined(LSK_ELEM_F32)
+typedef float elem_t;
+typedef float elem8 __attribute__((ext_vector_type(8)));
+// gfx950 has no xf32 MFMA: the 16x16x32 product of the 16-bit builds is eight exact-fp32 v_mfma_f32_16x16x4_f32.  A 16x16x32 operand
+// gives lane l the elements [l & 15][(l >> 4) * 8 + 0..7]; the 16x16x4 form takes [l & 15][k = l >> 4], one per lane, so issue j, fed
+// element j of every lane, sums k in {j, 8 + j, 16 + j, 24 + j} and the eight issues cover the 32 k.  Every fragment address, packed
+// layout index and C-layout consumer of the kernels stays valid as it is, and the summation order is a function of K alone (row invariance).
+__device__ __forceinline__ f32x4 lsk_mfma_f32_16x16x32(const elem8& a, const elem8& b, f32x4 c, int, int, int) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], c, 0, 0, 0);
+    return c;
+}
+#define LSK_MFMA_16x16x32 lsk_mfma_f32_16x16x32
+#define LSK_ELEM_DTYPE 2
+#define LSK_EB 4               // bytes per element
+#define LSK_SPW 8              // half the k-steps of the 16-bit builds: the same 64-register weight ring and the same K-chunk bytes in LDS
+#elif defined(LSK_ELEM_F16)
 typedef _Float16 elem_t;
 typedef _Float16 elem8 __attribute__((ext_vector_type(8)));
 #define LSK_MFMA_16x16x32 __builtin_amdgcn_mfma_f32_16x16x32_f16
 #define LSK_ELEM_DTYPE 1
+#define LSK_EB 2
 #else
 typedef __bf16 elem_t;
 typedef __bf16 elem8 __attribute__((ext_vector_type(8)));
 #define LSK_MFMA_16x16x32 __builtin_amdgcn_mfma_f32_16x16x32_bf16
 #define LSK_ELEM_DTYPE 0
+#define LSK_EB 2
 #endif
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+static_assert(LSK_EB == sizeof(elem_t), "element bytes");   // a lane's 8-element fragment is 8 LSK_EB bytes, a k-step of a packed tile 512 LSK_EB
+#define LSK_LPF (LSK_EB / 2)               // 16-byte loads per lane fragment: 1 (bf16, fp16) or 2 (fp32)
 
 #define LSK_WAVES 8            // waves per projection workgroup at most (the split-K factor inside a workgroup is 8 or 4: lsk_gemm_waves, lsk_gemm.h)
+#ifndef LSK_SPW
 #define LSK_SPW 16             // k-steps per wave per (tile, chunk) unit = depth of the weight ring
+#endif
 #ifndef LSK_FORCE_WAVES
 #define LSK_FORCE_WAVES 0      // measurement builds: -DLSK_FORCE_WAVES=8 (rounds 1-5's shape everywhere) or 4
 #endif
@@ -37,6 +60,7 @@ static_assert((1 << LSK_PAGE_SHIFT) == LSK_ATTN_PAGE, "page shift");
 __device__ __forceinline__ int lsk_tph_shift(int head_dim) { return head_dim == 128 ? 3 : 2; }
 #define LSK_SAMPLE_REG_VOCAB 32768  // sample=True: rows of up to this many logits live in one workgroup's registers (lsk_sample.h)
 
+// (fp32: both are identities -- the reference's fp32 run rounds nowhere)
 __device__ __forceinline__ float e2f(elem_t v) { return (float)v; }
 __device__ __forceinline__ elem_t f2e(float v) { return (elem_t)v; }   // round-to-nearest-even
 // One rounding to the model dtype, result widened again (the reference rounds wherever HF's

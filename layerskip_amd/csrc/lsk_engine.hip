@@ -76,18 +76,18 @@ static WsLayout ws_layout(const lsk_config* c) {
     L.bulk_ids = take(sizeof(int) * (size_t)(c->max_prompt + 16));
     L.part_val = take(sizeof(float) * 16 * (size_t)L.max_parts);
     L.part_idx = take(sizeof(int) * 16 * (size_t)L.max_parts);
-    L.hrow = take(2 * (size_t)LSK_MAX_ROWS * c->hidden);
-    L.hmsg = take(2 * (size_t)(LSK_MAX_ROWS + 1) * c->hidden);
-    L.hbulk = take(2 * (size_t)(c->max_prompt + 16) * c->hidden);
-    L.qbuf = take(2 * (size_t)LSK_MAX_ROWS * c->n_heads * c->head_dim);
-    L.attn = take(2 * (size_t)LSK_MAX_ROWS * c->n_heads * c->head_dim);
-    L.act = take(2 * (size_t)LSK_MAX_ROWS * c->intermediate);
+    L.hrow = take(sizeof(elem_t) * (size_t)LSK_MAX_ROWS * c->hidden);
+    L.hmsg = take(sizeof(elem_t) * (size_t)(LSK_MAX_ROWS + 1) * c->hidden);
+    L.hbulk = take(sizeof(elem_t) * (size_t)(c->max_prompt + 16) * c->hidden);
+    L.qbuf = take(sizeof(elem_t) * (size_t)LSK_MAX_ROWS * c->n_heads * c->head_dim);
+    L.attn = take(sizeof(elem_t) * (size_t)LSK_MAX_ROWS * c->n_heads * c->head_dim);
+    L.act = take(sizeof(elem_t) * (size_t)LSK_MAX_ROWS * c->intermediate);
     L.attn_part = take(sizeof(float) * (size_t)c->n_heads * L.n_pages * LSK_MAX_ROWS * (c->head_dim + 2));
     L.attn_cnt = take(sizeof(int) * (size_t)(c->n_heads + 16));   // arrival tickets per head column
-    L.xn_bulk = take(2 * (size_t)(c->max_prompt + 16) * c->hidden);
-    L.q_bulk = take(2 * (size_t)(c->max_prompt + 16) * c->n_heads * c->head_dim);
-    L.attn_bulk = take(2 * (size_t)(c->max_prompt + 16) * c->n_heads * c->head_dim);
-    L.act_bulk = take(2 * (size_t)(c->max_prompt + 16) * c->intermediate);
+    L.xn_bulk = take(sizeof(elem_t) * (size_t)(c->max_prompt + 16) * c->hidden);
+    L.q_bulk = take(sizeof(elem_t) * (size_t)(c->max_prompt + 16) * c->n_heads * c->head_dim);
+    L.attn_bulk = take(sizeof(elem_t) * (size_t)(c->max_prompt + 16) * c->n_heads * c->head_dim);
+    L.act_bulk = take(sizeof(elem_t) * (size_t)(c->max_prompt + 16) * c->intermediate);
     // large-vocabulary sampling state (LSK_SAMPLE_BIG_VOCAB, lsk_sample.h): 17 rows x 65 536 keys
     L.samp_big = c->vocab > LSK_SAMPLE_REG_VOCAB;
     const size_t srows = LSK_MAX_ROWS + 1;
@@ -111,15 +111,15 @@ extern "C" int lsk_workspace_bytes(const lsk_config* cfg, size_t* out_bytes) {
 extern "C" int lsk_kv_pool_bytes(const lsk_config* cfg, size_t* out_bytes) {
     LSK_TRY(lsk_check_cfg(cfg));
     if (!out_bytes) return lsk_fail("null out");
-    // [layer][K|V][page][kv_head][slot][head_dim] bf16
-    *out_bytes = (size_t)cfg->num_layers * 2 * (size_t)cfg->max_ctx * cfg->n_kv_heads * cfg->head_dim * 2;
+    // [layer][K|V][page][kv_head][slot][head_dim] elem_t
+    *out_bytes = (size_t)cfg->num_layers * 2 * (size_t)cfg->max_ctx * cfg->n_kv_heads * cfg->head_dim * sizeof(elem_t);
     return 0;
 }
 
 extern "C" int lsk_packed_bytes(int32_t n_rows, int32_t k, size_t* out_bytes) {
     if (!out_bytes) return lsk_fail("lsk_packed_bytes: null out");
     if (n_rows <= 0 || k <= 0 || (k % 32)) return lsk_fail("lsk_packed_bytes: n_rows=%d k=%d (k must be a multiple of 32)", n_rows, k);
-    *out_bytes = (size_t)((n_rows + 15) / 16) * 16 * (size_t)k * 2;
+    *out_bytes = (size_t)((n_rows + 15) / 16) * 16 * (size_t)k * sizeof(elem_t);
     return 0;
 }
 
@@ -420,7 +420,7 @@ static int launch_attn(lsk_engine* e, const elem_t* q, elem_t* out, const elem_t
 #endif
     hipEvent_t ea = nullptr, eb = nullptr;
     // algorithmic bytes: K and V of every key in reach, once (GQA: each KV head once)
-    LSK_TRY(profile_pair(e, LSK_PROF_ATTN, m, 2.0 * 2.0 * c.n_kv_heads * hd * (double)(e->kv_len_host + pos_off + m), &ea, &eb));
+    LSK_TRY(profile_pair(e, LSK_PROF_ATTN, m, 2.0 * (double)sizeof(elem_t) * c.n_kv_heads * hd * (double)(e->kv_len_host + pos_off + m), &ea, &eb));
     const lsk_attn_split_fn kern = lsk_attn_split_for(hd, sp.counters != nullptr);
     if (ea != nullptr) hipExtLaunchKernelGGL(kern, grid, block, 0, st, ea, eb, 0, LSK_ATTN_HOT_ARGS(sp));
     else hipLaunchKernelGGL(kern, grid, block, 0, st, LSK_ATTN_HOT_ARGS(sp));
@@ -459,7 +459,7 @@ int lsk_run_layers_dev(lsk_engine* e, elem_t* x, int m, const int* base_ptr, int
             GemmParams p{};
             p.x = x; p.ldx = c.hidden; p.M = m; p.K = c.hidden;
             p.N = qdim + 2 * kvdim; p.n_tiles = p.N / 16;
-            p.wp = lw.wqkv; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * 2);
+            p.wp = lw.wqkv; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * sizeof(elem_t));
             p.norm_w = lw.norm1; p.eps = c.rms_eps;
             p.q_out = e->qbuf; p.ldq = qdim; p.kpool = kpool; p.vpool = vpool; p.block_table = e->block_table;
             p.page_size = c.page_size; p.n_heads = c.n_heads; p.n_kv = c.n_kv_heads; p.head_dim = c.head_dim;
@@ -472,7 +472,7 @@ int lsk_run_layers_dev(lsk_engine* e, elem_t* x, int m, const int* base_ptr, int
         {   // o_proj + residual
             GemmParams p{};
             p.x = e->attn; p.ldx = qdim; p.M = m; p.K = qdim; p.N = c.hidden; p.n_tiles = p.N / 16;
-            p.wp = lw.wo; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * 2);
+            p.wp = lw.wo; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * sizeof(elem_t));
             p.h = x; p.ldh = c.hidden;
             hipEvent_t ea = nullptr, eb = nullptr;
             LSK_TRY(profile_pair(e, LSK_PROF_OPROJ, m, (double)p.wp_bytes, &ea, &eb));
@@ -481,7 +481,7 @@ int lsk_run_layers_dev(lsk_engine* e, elem_t* x, int m, const int* base_ptr, int
         {   // post-attention RMSNorm -> gate/up -> SiLU * up
             GemmParams p{};
             p.x = x; p.ldx = c.hidden; p.M = m; p.K = c.hidden; p.N = 2 * c.intermediate; p.n_tiles = p.N / 16;
-            p.wp = lw.wgu; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * 2);
+            p.wp = lw.wgu; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * sizeof(elem_t));
             p.norm_w = lw.norm2; p.eps = c.rms_eps; p.act = e->act; p.ldact = c.intermediate;
             hipEvent_t ea = nullptr, eb = nullptr;
             LSK_TRY(profile_pair(e, LSK_PROF_GATEUP, m, (double)p.wp_bytes, &ea, &eb));
@@ -490,7 +490,7 @@ int lsk_run_layers_dev(lsk_engine* e, elem_t* x, int m, const int* base_ptr, int
         {   // down_proj + residual
             GemmParams p{};
             p.x = e->act; p.ldx = c.intermediate; p.M = m; p.K = c.intermediate; p.N = c.hidden; p.n_tiles = p.N / 16;
-            p.wp = lw.wdown; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * 2);
+            p.wp = lw.wdown; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * sizeof(elem_t));
             p.h = x; p.ldh = c.hidden;
             hipEvent_t ea = nullptr, eb = nullptr;
             LSK_TRY(profile_pair(e, LSK_PROF_DOWN, m, (double)p.wp_bytes, &ea, &eb));
@@ -508,7 +508,7 @@ int lsk_run_head_dev(lsk_engine* e, const elem_t* x, int m, float* logits, int l
     if (embed_dst != nullptr && !e->embed) return lsk_fail("the embedding is not bound on this engine");
     GemmParams p{};
     p.x = x; p.ldx = c.hidden; p.M = m; p.K = c.hidden; p.N = c.vocab; p.n_tiles = (c.vocab + 15) / 16;
-    p.wp = e->lm_head; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * 2);
+    p.wp = e->lm_head; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * sizeof(elem_t));
     p.norm_w = e->final_norm; p.eps = c.rms_eps;
     p.logits = logits; p.ld_logits = ld_logits; p.part_val = e->part_val; p.part_idx = e->part_idx;
     int grid = 0;
@@ -570,6 +570,9 @@ static int launch_big(BigGemmParams& p, hipStream_t st) {
 // count that leaves half the chip a second round to itself (128 x 256 at 1023 rows of a 12 288-feature q/k/v: 384 workgroups at one per
 // CU, 133 us against 114 for 512 workgroups of 128 x 192).
 static int launch_big_qkv(BigGemmParams& p, hipStream_t st) {
+#if LSK_EB == 4
+    return launch_big<EPI_QKV, 2, 4, 2, 4, false>(p, st);   // fp32: one 64 x 128 shape (twice the fragment registers: the larger tiles would spill)
+#else
     // cost of a shape = (workgroups on the busiest CU) x (tile area) / (TFLOP/s a CU sustains on that shape), the rates read off the table:
     // ~3.7-3.8 for the eight-wave tiles, 3.45 for 128-row four-wave tiles once a CU holds two of them (2.85 alone: one wave per SIMD),
     // 2.2-2.8 for 64-row tiles.  llama2-7B (N = 12 288): 64 x 128 up to 191 rows, 64 x 192 to 319, 128 x 192 to 639, 128 x 384 where it is
@@ -594,11 +597,21 @@ static int launch_big_qkv(BigGemmParams& p, hipStream_t st) {
         case 1: return launch_big<EPI_QKV, 3, 4, 2, 4, false>(p, st);
         default: return launch_big<EPI_QKV, 2, 4, 2, 4, false>(p, st);
     }
+#endif
 }
 
-static int launch_big_gateup(BigGemmParams& p, hipStream_t st) { return launch_big<EPI_SWIGLU, 2, 8, 2, 4, false, 1, false>(p, st); }
+static int launch_big_gateup(BigGemmParams& p, hipStream_t st) {
+#if LSK_EB == 4
+    return launch_big<EPI_SWIGLU, 2, 4, 2, 4, false, 1, false>(p, st);
+#else
+    return launch_big<EPI_SWIGLU, 2, 8, 2, 4, false, 1, false>(p, st);
+#endif
+}
 
 static int launch_big_resid(BigGemmParams& p, hipStream_t st) {
+#if LSK_EB == 4
+    return launch_big<EPI_RESID, 2, 4, 2, 4, false>(p, st);
+#else
     const int panels = (p.n_tiles + 7) / 8;
     const int rb128 = (p.M + 127) / 128;
     // N = hidden is few panels: while a shape gives <= one workgroup per CU, K-split 2 (eight waves per workgroup, the two halves of K side
@@ -617,6 +630,7 @@ static int launch_big_resid(BigGemmParams& p, hipStream_t st) {
     if (rb128 * panels > 256 && (w256 <= 256 || w256 >= 512)) return launch_big<EPI_RESID, 2, 8, 2, 8, true>(p, st);
     if (rb128 * panels >= 512) return launch_big<EPI_RESID, 2, 8, 2, 4, false>(p, st);
     return launch_big<EPI_RESID, 2, 4, 4, 4, true>(p, st);
+#endif
 }
 
 // Prompt rows [0, n) of the bulk buffer through layers [lb, le) with the MFMA-tiled prefill kernels.
@@ -764,14 +778,14 @@ extern "C" int lsk_run_head(lsk_engine* e, int32_t buffer, int32_t row_base, int
 extern "C" int lsk_read_rows(lsk_engine* e, int32_t buffer, int32_t row_base, int32_t m, void* dst, void* stream) {
     if (!e || !dst || m < 1) return lsk_fail("lsk_read_rows: bad arguments");
     if (buffer < 0 || buffer > 2 || row_base < 0 || row_base + m > lsk_buf_capacity(e, buffer)) return lsk_fail("lsk_read_rows: rows out of range");
-    HIP_OK(hipMemcpyAsync(dst, lsk_buf_rows(e, buffer, row_base), (size_t)m * e->cfg.hidden * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIP_OK(hipMemcpyAsync(dst, lsk_buf_rows(e, buffer, row_base), (size_t)m * e->cfg.hidden * sizeof(elem_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 
 extern "C" int lsk_write_rows(lsk_engine* e, int32_t buffer, int32_t row_base, int32_t m, const void* src, void* stream) {
     if (!e || !src || m < 1) return lsk_fail("lsk_write_rows: bad arguments");
     if (buffer < 0 || buffer > 2 || row_base < 0 || row_base + m > lsk_buf_capacity(e, buffer)) return lsk_fail("lsk_write_rows: rows out of range");
-    HIP_OK(hipMemcpyAsync(lsk_buf_rows(e, buffer, row_base), src, (size_t)m * e->cfg.hidden * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIP_OK(hipMemcpyAsync(lsk_buf_rows(e, buffer, row_base), src, (size_t)m * e->cfg.hidden * sizeof(elem_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 
@@ -791,7 +805,7 @@ extern "C" int lsk_time_gateup(lsk_engine* e, int32_t layer, int32_t m, int32_t 
         const LayerWeights& lw = e->layers[(layer + i) % c.num_layers];
         GemmParams p{};
         p.x = e->hrow; p.ldx = c.hidden; p.M = m; p.K = c.hidden; p.N = 2 * c.intermediate; p.n_tiles = p.N / 16;
-        p.wp = lw.wgu; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * 2);
+        p.wp = lw.wgu; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * sizeof(elem_t));
         p.norm_w = lw.norm2; p.eps = c.rms_eps; p.act = e->act; p.ldact = c.intermediate;
         rc = launch_gemm<PRO_RMS, EPI_SWIGLU>(p, e->target_wgs, st);
     }

@@ -61,11 +61,33 @@ __device__ __forceinline__ UnitInfo lsk_unit_info(int u, int units, int ntl, int
     const int ks0 = w * spw;
     r.c = c; r.tl = tl; r.ks0 = ks0; r.steps_c = steps_c;
     r.nvalid = max(0, min(spw, steps_c - ks0));
-    r.off0 = ((unsigned)(tile0 + tl) * (unsigned)ksteps + (unsigned)(c * KC_STEPS + ks0)) * 1024u + (unsigned)lane * 16u;
+    r.off0 = ((unsigned)(tile0 + tl) * (unsigned)ksteps + (unsigned)(c * KC_STEPS + ks0)) * (unsigned)(512 * LSK_EB) + (unsigned)lane * (unsigned)(8 * LSK_EB);
     return r;
 }
 
 #define LSK_OOB_OFFSET 0xF0000000u
+
+// Ring slot s <- this wave's fragment of k-step s of unit `u` (out of range: the bounds check returns zeros, moves no bytes).  A lane's
+// fragment is 8 elements: one 16-byte load in the 16-bit builds, two (the halves of its 32 contiguous bytes) in the fp32 build.
+#if LSK_LPF == 1
+#define lsk_ring_fill(ring, s, rsrc, u, valid) do { \
+        const unsigned lsk_off = (valid) ? (u).off0 + (unsigned)(s) * 1024u : LSK_OOB_OFFSET; \
+        (ring)[s] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lsk_off, 0, 2 /* nt */); \
+    } while (0)
+#else
+#define lsk_ring_fill(ring, s, rsrc, u, valid) do { \
+        const unsigned lsk_off = (valid) ? (u).off0 + (unsigned)(s) * (unsigned)(512 * LSK_EB) : LSK_OOB_OFFSET; \
+        (ring)[2 * (s)] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lsk_off, 0, 2 /* nt */); \
+        (ring)[2 * (s) + 1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (valid) ? lsk_off + 16u : LSK_OOB_OFFSET, 0, 2 /* nt */); \
+    } while (0)
+#endif
+__device__ __forceinline__ elem8 lsk_ring_frag(const u32x4 (&ring)[LSK_SPW * LSK_LPF], int s) {
+#if LSK_LPF == 1
+    return __builtin_bit_cast(elem8, ring[s]);
+#else
+    return __builtin_bit_cast(elem8, __builtin_shufflevector(ring[2 * s], ring[2 * s + 1], 0, 1, 2, 3, 4, 5, 6, 7));
+#endif
+}
 
 // ---- workgroup geometry: NW waves split the k-steps of a K-chunk of NW x 16 x 32 features, 16 k-steps (= the ring depth) per wave ----
 // 8 waves / 4096-feature chunks are the shape of rounds 1-5.  Round 6 (profiles/r06_ab_1B_options.json,
@@ -79,7 +101,10 @@ __device__ __forceinline__ UnitInfo lsk_unit_info(int u, int units, int ntl, int
 // A function of (kernel, K) only -- never of the row count -- so the summation order of an output element still depends on nothing
 // but its projection: row invariance holds.
 __host__ __device__ inline int lsk_kc_elems(int nw) { return nw * LSK_SPW * 32; }
+// fp32: always four waves -- one wave per SIMD keeps the 512-register budget the doubled row and fragment registers need (the eight-wave
+// multi-row forms spill at 256).
 __host__ inline int lsk_gemm_waves(int pro, int epi, int K) {
+    if (LSK_EB == 4) return 4;
     if (LSK_FORCE_WAVES) return LSK_FORCE_WAVES;
     return (pro == PRO_PLAIN || epi == EPI_HEAD || K <= 2048 || K > 4096) ? 4 : 8;
 }
@@ -94,7 +119,7 @@ __host__ inline int lsk_gemm_waves(int pro, int epi, int K) {
 
 // +32 B per row: the 16-B slot of (row r, k-group g) in a 256-B bank row is (2r + g) mod 16, a bijection inside every
 // 16-lane service group of ds_read_b128 (with +16 B it was r + g: 2-way conflicts, SQ_LDS_BANK_CONFLICT 34 % at M = 7)
-__host__ __device__ inline int lsk_gemm_xstride(int K, int nw) { return (K < lsk_kc_elems(nw) ? K : lsk_kc_elems(nw)) * 2 + 32; }
+__host__ __device__ inline int lsk_gemm_xstride(int K, int nw) { return (K < lsk_kc_elems(nw) ? K : lsk_kc_elems(nw)) * LSK_EB + 32; }
 __host__ inline size_t lsk_gemm_lds_bytes(int M, int K, int nw) { return (size_t)LSK_LDS_X + (size_t)M * lsk_gemm_xstride(K, nw); }
 
 // Activation staging is split in two so that no global load of x ever sits BEHIND the weight ring in a
@@ -154,7 +179,7 @@ __device__ __forceinline__ void lsk_store_chunk(const GemmHot& p, unsigned char*
                         v[j] = f2e(e2f(nw[j]) * xn);                   // weight * that, rounded again
                     }
                 }
-                *(elem8*)(xs + (size_t)i * xstride + e0 * 2) = v;
+                *(elem8*)(xs + (size_t)i * xstride + e0 * LSK_EB) = v;
             }
         }
     }
@@ -245,7 +270,7 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
     elem8 nw = {};
     float ss[MB];
     float sv[MB];                 // per-row 1/rms (PRO_RMS), wave-uniform
-    u32x4 ring[LSK_SPW];
+    u32x4 ring[LSK_SPW * LSK_LPF];      // fp32: two 16-byte halves per fragment (lsk_ring_fill)
     // Multi-row RMSNorm launches of a one-chunk K (the verify pass's q/k/v, gate/up and lm_head at hidden <= 4096): the normalisation
     // of 8 rows is ~450 VALU instructions per thread, ~2 us for the CU whoever executes them, and it used to start only when the LAST
     // wave was through the throttled issue of its ring (4.4 us: requests leave a CU at the HBM rate) -- a hole in the stream, rows staged
@@ -277,10 +302,7 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
                 for (int i = 0; i < MB; ++i) xr2[i] = *(const elem8*)(hp.x + (size_t)min(i, M - 1) * hp.ldx + k1);
             }
 #pragma unroll
-            for (int s = 0; s < LSK_SPW; ++s) {
-                const unsigned off = (s < cur.nvalid) ? cur.off0 + (unsigned)s * 1024u : LSK_OOB_OFFSET;
-                ring[s] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 2 /* nt */);
-            }
+            for (int s = 0; s < LSK_SPW; ++s) lsk_ring_fill(ring, s, rsrc, cur, s < cur.nvalid);
             lsk_accumulate_squares<MB>(xr, tid * 8 < cur.steps_c * 32, ss);
             lsk_accumulate_squares<MB>(xr2, (tid + THREADS / 2) * 8 < cur.steps_c * 32, ss2);
 #pragma unroll
@@ -306,10 +328,7 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
             lsk_store_chunk<PRO, MB>(hp, xs, xstride, sv, cur.steps_c, tid + THREADS / 2, xr2, nw2);
         } else {
 #pragma unroll
-            for (int s = 0; s < LSK_SPW; ++s) {
-                const unsigned off = (s < cur.nvalid) ? cur.off0 + (unsigned)s * 1024u : LSK_OOB_OFFSET;
-                ring[s] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 2 /* nt */);
-            }
+            for (int s = 0; s < LSK_SPW; ++s) lsk_ring_fill(ring, s, rsrc, cur, s < cur.nvalid);
         }
         LSK_TRACE_POINT(1);
     } else {
@@ -330,10 +349,7 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
         lsk_load_chunk<PRO, MB, NW>(hp, 0, cur.steps_c, tid, xr, nw);
     }
 #pragma unroll
-    for (int s = 0; s < LSK_SPW; ++s) {
-        const unsigned off = (s < cur.nvalid) ? cur.off0 + (unsigned)s * 1024u : LSK_OOB_OFFSET;
-        ring[s] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 2 /* nt */);
-    }
+    for (int s = 0; s < LSK_SPW; ++s) lsk_ring_fill(ring, s, rsrc, cur, s < cur.nvalid);
     LSK_TRACE_POINT(1);                                           // rows and weight ring requested
     if (PRO == PRO_RMS) {
         lsk_accumulate_squares<MB>(xr, tid * 8 < cur.steps_c * 32, ss);
@@ -388,7 +404,7 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
     }
 
     const int arow = min(lane & 15, M - 1);
-    const unsigned char* xa = xs + (size_t)arow * xstride + (lane >> 4) * 16;
+    const unsigned char* xa = xs + (size_t)arow * xstride + (lane >> 4) * (8 * LSK_EB);
 
     f32x4 own0 = {0.f, 0.f, 0.f, 0.f};
     f32x4 own1 = {0.f, 0.f, 0.f, 0.f};
@@ -400,7 +416,7 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
     // every MFMA the LDS latency was exposed ~8x per unit and the ring refills queued up behind it).
     elem8 afr[LSK_SPW];
 #pragma unroll
-    for (int s = 0; s < LSK_SPW; ++s) afr[s] = *(const elem8*)(xa + min(cur.ks0 + s, cur.steps_c - 1) * 64);
+    for (int s = 0; s < LSK_SPW; ++s) afr[s] = *(const elem8*)(xa + min(cur.ks0 + s, cur.steps_c - 1) * (32 * LSK_EB));
 
     for (int u = 0; u < units; ++u) {
         const UnitInfo nxt = lsk_unit_info<NW>(u + 1, units, ntl, ksteps, tile0, w, lane);
@@ -412,18 +428,17 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
                 lsk_load_chunk<PRO, MB, NW>(hp, cur.c + 1, min(KC_STEPS, ksteps - (cur.c + 1) * KC_STEPS), tid, xr, nw);
             __syncthreads();
 #pragma unroll
-            for (int s = 0; s < LSK_SPW; ++s) afr[s] = *(const elem8*)(xa + min(cur.ks0 + s, cur.steps_c - 1) * 64);
+            for (int s = 0; s < LSK_SPW; ++s) afr[s] = *(const elem8*)(xa + min(cur.ks0 + s, cur.steps_c - 1) * (32 * LSK_EB));
         }
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < LSK_SPW; ++s) {
-            acc = LSK_MFMA_16x16x32(afr[s], __builtin_bit_cast(elem8, ring[s]), acc, 0, 0, 0);
+            acc = LSK_MFMA_16x16x32(afr[s], lsk_ring_frag(ring, s), acc, 0, 0, 0);
 #ifdef LSK_TRACE
             if (u == 0 && s == 0) LSK_TRACE_POINT(3);             // first weight fragment arrived
             if (u == 0 && s == LSK_SPW - 1) LSK_TRACE_POINT(4);   // first unit's fragments all arrived
 #endif
-            const unsigned off = (s < nxt.nvalid) ? nxt.off0 + (unsigned)s * 1024u : LSK_OOB_OFFSET;
-            ring[s] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 2 /* nt */);
+            lsk_ring_fill(ring, s, rsrc, nxt, s < nxt.nvalid);
             // (hipcc sinks these refills into bursts behind later MFMAs, so the ring runs ~8-16 deep; pinning
             //  "consume s -> refill s" with sched_barrier(0) gives the textbook vmcnt(15) stream but measured
             //  0..-4 % on every shape -- the HBM pipe is already full at ~8 KiB per wave in flight)

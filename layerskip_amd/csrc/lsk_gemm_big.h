@@ -20,7 +20,7 @@
 #include "lsk_common.h"
 
 #define LSK_BIG_BK 64
-#define LSK_BIG_LDA 160          // bytes per LDS row: 64 bf16 + 32 B pad (slot (10r + g) mod 16: conflict-free A-fragment reads)
+#define LSK_BIG_LDA (64 * LSK_EB + 32)   // bytes per LDS row: 64 elements + 32 B pad (bf16: slot (10r + g) mod 16, conflict-free A-fragment reads)
 
 struct BigGemmParams {
     const elem_t* x;        // [M][ldx]
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(NW * KS * 64, 2) void lsk_gemm_big_kernel(const Big
     for (int i = 0; i < NP; ++i) {
         const int r = arow + SR * i;
         aptr_i[i] = p.x + (size_t)min(m0 + r, p.M - 1) * p.ldx + acol * 8;
-        awr_i[i] = lds + r * LSK_BIG_LDA + acol * 16;
+        awr_i[i] = lds + r * LSK_BIG_LDA + acol * (8 * LSK_EB);
     }
     // B fragments: packed tile T, k-step s at ((T*ksteps + s)*64 + lane)*8 elements.  A wave whose tile lies beyond the matrix
     // (last panel of a ragged N) streams the last valid tile instead and drops the result: every load of the K loop is
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(NW * KS * 64, 2) void lsk_gemm_big_kernel(const Big
     // nkt is a multiple of PB (the host picks PB accordingly); indices past the end are clamped to the last
     // tile (a few redundant loads at the tail) so that the loop body has no data-dependent branch and every wait is counted
     const int last = nkt - 1;
-    const unsigned char* ard = lds + (lane & 15) * LSK_BIG_LDA + (lane >> 4) * 16;
+    const unsigned char* ard = lds + (lane & 15) * LSK_BIG_LDA + (lane >> 4) * (8 * LSK_EB);
     load_a(0, aq[0]);
     load_a(min(1, last), aq[1]);
 #pragma unroll
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(NW * KS * 64, 2) void lsk_gemm_big_kernel(const Big
             for (int s = 0; s < 2; ++s) {
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
-                    const elem8 a = *(const elem8*)(abase + mt * 16 * LSK_BIG_LDA + s * 64);
+                    const elem8 a = *(const elem8*)(abase + mt * 16 * LSK_BIG_LDA + s * (32 * LSK_EB));
 #pragma unroll
                     for (int nt = 0; nt < NTW; ++nt)
                         acc[mt][nt] = TR ? LSK_MFMA_16x16x32(bq[u][nt][s], a, acc[mt][nt], 0, 0, 0) : LSK_MFMA_16x16x32(a, bq[u][nt][s], acc[mt][nt], 0, 0, 0);

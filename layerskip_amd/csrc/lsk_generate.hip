@@ -574,7 +574,7 @@ extern "C" int lsk_get_row_tokens(lsk_engine* e, int32_t row0, int32_t n, int32_
 extern "C" int lsk_shift_rows(lsk_engine* e, int32_t src, int32_t dst, int32_t n, void* stream) {
     if (!e || n < 1 || dst < 0 || src <= dst || src + n > LSK_MAX_ROWS + 1) return lsk_fail("lsk_shift_rows: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    const size_t row_bytes = (size_t)e->cfg.hidden * 2;
+    const size_t row_bytes = (size_t)e->cfg.hidden * sizeof(elem_t);
     const int nr = src + n > LSK_MAX_ROWS ? LSK_MAX_ROWS - src : n;      // hidden rows (the token array has one more entry)
     for (int i = 0; i < nr; ++i)      // ascending: dst < src, regions may overlap
         HIP_OK(hipMemcpyAsync((char*)e->hrow + (size_t)(dst + i) * row_bytes, (char*)e->hrow + (size_t)(src + i) * row_bytes, row_bytes,

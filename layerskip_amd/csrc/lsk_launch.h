@@ -29,7 +29,9 @@ static int set_gemm_attr_nw() {
 template <int PRO, int EPI>
 static int set_gemm_attr() {
     LSK_TRY((set_gemm_attr_nw<PRO, EPI, 4>()));
+#if LSK_EB == 2
     LSK_TRY((set_gemm_attr_nw<PRO, EPI, 8>()));
+#endif
     return 0;
 }
 
@@ -97,7 +99,7 @@ static int launch_gemm_nw(GemmParams& p, int target_wgs, hipStream_t st, int* gr
     if (p.n_tiles != (p.N + 15) / 16) return lsk_fail("gemm: n_tiles %d is not ceil(N / 16) of N = %d", p.n_tiles, p.N);   // the kernel derives it
     if (lds > kMaxGemmLds) return lsk_fail("gemm LDS %zu exceeds %zu", lds, kMaxGemmLds);
     // 32-bit buffer offsets; the out-of-range sentinel of ragged ring slots must stay beyond the descriptor's range
-    if ((size_t)p.n_tiles * 16 * (size_t)p.K * 2 >= (size_t)LSK_OOB_OFFSET) return lsk_fail("packed weight of %d x %d exceeds the 32-bit buffer range", p.n_tiles * 16, p.K);
+    if ((size_t)p.n_tiles * 16 * (size_t)p.K * sizeof(elem_t) >= (size_t)LSK_OOB_OFFSET) return lsk_fail("packed weight of %d x %d exceeds the 32-bit buffer range", p.n_tiles * 16, p.K);
 #ifdef LSK_TRACE
     p.trace = lsk_trace_next(0, (PRO * 16 + EPI) | (p.K << 8), p.M, grid);
 #endif
@@ -116,8 +118,12 @@ static int launch_gemm_nw(GemmParams& p, int target_wgs, hipStream_t st, int* gr
 template <int PRO, int EPI>
 static int launch_gemm(GemmParams& p, int target_wgs, hipStream_t st, int* grid_out = nullptr, hipEvent_t ev_start = nullptr,
                        hipEvent_t ev_stop = nullptr) {
+#if LSK_EB == 4
+    return launch_gemm_nw<PRO, EPI, 4>(p, target_wgs, st, grid_out, ev_start, ev_stop);   // (lsk_gemm_waves: the eight-wave forms are not built)
+#else
     if (lsk_gemm_waves(PRO, EPI, p.K) == 4) return launch_gemm_nw<PRO, EPI, 4>(p, target_wgs, st, grid_out, ev_start, ev_stop);
     return launch_gemm_nw<PRO, EPI, 8>(p, target_wgs, st, grid_out, ev_start, ev_stop);
+#endif
 }
 
 #ifndef LSK_PF_RT
@@ -143,9 +149,13 @@ static int launch_attn_prefill_rt(const AttnPrefillParams& ap, int n_heads, int 
 // profiles/r06_prefill_attention_variants.txt.  The two-tile form also sums a row's probabilities in the order of rounds 2-5
 // (lsk_pf_row_sum: prompt KV bit-identical to the earlier rounds); otherwise a row's result does not depend on the choice (lsk_attn.h).
 static int launch_attn_prefill(const AttnPrefillParams& ap, int n_heads, int head_dim, int rows, hipStream_t st) {
+#if LSK_EB == 4
+    return launch_attn_prefill_rt<1>(ap, n_heads, head_dim, rows, st);   // fp32: one row tile per workgroup (twice the fragment registers)
+#else
     if (LSK_PF_RT == 1) return launch_attn_prefill_rt<1>(ap, n_heads, head_dim, rows, st);
     if (LSK_PF_RT == 2) return launch_attn_prefill_rt<2>(ap, n_heads, head_dim, rows, st);
     if (LSK_PF_RT == 3) return launch_attn_prefill_rt<3>(ap, n_heads, head_dim, rows, st);
     return rows > LSK_PF_RT_LONG_ROWS ? launch_attn_prefill_rt<3>(ap, n_heads, head_dim, rows, st) : launch_attn_prefill_rt<2>(ap, n_heads, head_dim, rows, st);
+#endif
 }
 

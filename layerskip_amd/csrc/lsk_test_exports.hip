@@ -53,7 +53,7 @@ extern "C" int lsk_test_gemm(const void* x, int32_t m, int32_t k, const void* w_
     LSK_TRY(init_kernel_attrs());
     GemmParams p{};
     p.x = (const elem_t*)x; p.ldx = k; p.M = m; p.K = k; p.N = n_rows; p.n_tiles = (n_rows + 15) / 16;
-    p.wp = (const elem_t*)w_packed; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * k * 2);
+    p.wp = (const elem_t*)w_packed; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * k * sizeof(elem_t));
     p.norm_w = (const elem_t*)norm_w; p.eps = eps; p.y = y;
     const int tw = target_wgs > 0 ? target_wgs : 256;
     return norm_w ? launch_gemm<PRO_RMS, EPI_F32>(p, tw, (hipStream_t)stream) : launch_gemm<PRO_PLAIN, EPI_F32>(p, tw, (hipStream_t)stream);
@@ -87,7 +87,7 @@ extern "C" int lsk_test_qkv(const void* x, int32_t m, int32_t hidden, const void
     const int qdim = n_heads * head_dim, kvdim = n_kv_heads * head_dim;
     GemmParams p{};
     p.x = (const elem_t*)x; p.ldx = hidden; p.M = m; p.K = hidden; p.N = qdim + 2 * kvdim; p.n_tiles = p.N / 16;
-    p.wp = (const elem_t*)wqkv_packed; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * 2);
+    p.wp = (const elem_t*)wqkv_packed; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * sizeof(elem_t));
     p.norm_w = (const elem_t*)norm_w; p.eps = eps;
     p.q_out = (elem_t*)q_out; p.ldq = qdim; p.kpool = (elem_t*)kpool; p.vpool = (elem_t*)vpool; p.block_table = block_table_dev;
     p.page_size = LSK_ATTN_PAGE; p.n_heads = n_heads; p.n_kv = n_kv_heads; p.head_dim = head_dim;
@@ -103,7 +103,7 @@ extern "C" int lsk_test_swiglu(const void* x, int32_t m, int32_t hidden, const v
     LSK_TRY(init_kernel_attrs());
     GemmParams p{};
     p.x = (const elem_t*)x; p.ldx = hidden; p.M = m; p.K = hidden; p.N = 2 * intermediate; p.n_tiles = p.N / 16;
-    p.wp = (const elem_t*)wgu_packed; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * 2);
+    p.wp = (const elem_t*)wgu_packed; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * sizeof(elem_t));
     p.norm_w = (const elem_t*)norm_w; p.eps = eps; p.act = (elem_t*)act_out; p.ldact = intermediate;
     return launch_gemm<PRO_RMS, EPI_SWIGLU>(p, 256, (hipStream_t)stream);
 }
@@ -115,7 +115,7 @@ extern "C" int lsk_test_resid(const void* x, int32_t m, int32_t k, const void* w
     LSK_TRY(init_kernel_attrs());
     GemmParams p{};
     p.x = (const elem_t*)x; p.ldx = k; p.M = m; p.K = k; p.N = n; p.n_tiles = n / 16;
-    p.wp = (const elem_t*)w_packed; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * 2);
+    p.wp = (const elem_t*)w_packed; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * sizeof(elem_t));
     p.h = (elem_t*)h_inout; p.ldh = n;
     return launch_gemm<PRO_PLAIN, EPI_RESID>(p, 256, (hipStream_t)stream);
 }
@@ -136,7 +136,7 @@ extern "C" int lsk_test_head(const void* x, int32_t m, int32_t hidden, const voi
     const int n_tiles = (vocab + 15) / 16;
     GemmParams p{};
     p.x = (const elem_t*)x; p.ldx = hidden; p.M = m; p.K = hidden; p.N = vocab; p.n_tiles = n_tiles;
-    p.wp = (const elem_t*)lm_head_packed; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * 2);
+    p.wp = (const elem_t*)lm_head_packed; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * sizeof(elem_t));
     p.norm_w = (const elem_t*)norm_w; p.eps = eps;
     p.logits = (float*)logits_out; p.ld_logits = ld_logits;
     p.part_val = (float*)scratch; p.part_idx = (int*)((float*)scratch + (size_t)n_tiles * 16);

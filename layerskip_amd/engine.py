@@ -93,9 +93,17 @@ class HipEngine:
         elif weight.dtype == torch.float16:
             # the fp16 library: the same sources built with -DLSK_ELEM_F16 (the dtype generate.py:63 hard-codes)
             self.dtype, dtype_name = torch.float16, "fp16"
+        elif weight.dtype == torch.float32:
+            # the fp32 library: -DLSK_ELEM_F32 (HF's default dtype, the one the reference's unit tests load)
+            self.dtype, dtype_name = torch.float32, "fp32"
         else:
-            raise _lib.LskError(f"HipEngine computes in bf16 (or fp16); model dtype is {weight.dtype}")
+            raise _lib.LskError(f"HipEngine computes in bf16, fp16 or fp32; model dtype is {weight.dtype}")
         self.lib = _lib.load(dtype=dtype_name)
+        self.elem_bytes = torch.empty(0, dtype=self.dtype).element_size()
+        # sample=True on the device: the sampler's 16-bit logit keys are exact at bf16 / fp16 only (lsk_key16, lsk_sample.h).  Over fp32
+        # logits they would merge distinct values and top-k / top-p would act on other sets than the reference's warpers, so the fp32
+        # engine offers no device-sampled entry point: the strategies read this flag and keep sampled steps on the host path.
+        self.samples_on_device = self.lib.lsk_elem_dtype() != _lib.DTYPE_CODES["fp32"]
         if getattr(cfg, "attention_bias", False) or getattr(cfg, "mlp_bias", False):
             raise _lib.LskError("biased projections are not supported")
         # The engine keeps its own references to every tensor it borrows (embedding, norm gains) and copies of the
@@ -162,11 +170,11 @@ class HipEngine:
             return None                      # the originals were dropped: the model object only serves this engine
         tensors = self._weight_tensors(m)
         meta = tuple((t.data_ptr(), t._version) for t in tensors)
-        if not self._handle or any(t.device != self.device or t.element_size() != 2 or not t.is_contiguous() for t in tensors):
+        if not self._handle or any(t.device != self.device or t.element_size() != self.elem_bytes or not t.is_contiguous() for t in tensors):
             return (meta, None)
         n = len(tensors)
         ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors])
-        cnts = (ctypes.c_int64 * n)(*[t.numel() for t in tensors])
+        cnts = (ctypes.c_int64 * n)(*[t.numel() * self.elem_bytes // 2 for t in tensors])    # the checksum samples 2-byte units
         sums = (ctypes.c_uint64 * n)()
         self._ck(self.lib.lsk_engine_weights_checksum(self._handle, ptrs, cnts, n, sums, self._stream))
         return (meta, tuple(sums))
@@ -394,6 +402,7 @@ class HipEngine:
 
     # ------------------------------------------------------------------ sampling on the device (opt-in)
     def _sampling_scratch(self) -> torch.Tensor:
+        self._check_device_sampling()
         buf = self._buffers.get("sampling")
         if buf is None:
             n = ctypes.c_size_t(0)
@@ -401,6 +410,10 @@ class HipEngine:
             buf = torch.empty(n.value, dtype=torch.uint8, device=self.device)
             self._buffers["sampling"] = buf
         return buf
+
+    def _check_device_sampling(self) -> None:
+        if not self.samples_on_device:
+            raise _lib.LskError(f"the {self.dtype} engine does not sample on the device (16-bit sampler keys); sample=True runs on the host path")
 
     def _sampling_args(self, temperature, top_k, top_p, seed, offset) -> tuple:
         """The sample=True arguments of a sampled entry point: warping, Philox key and counter, the sampling scratch."""
@@ -411,6 +424,7 @@ class HipEngine:
                     tag0: int = 0):
         """decode_next_token(sample=True) over rows of device logits [m, ld] (fp32).  Returns (tokens int32[m] on
         the device, probabilities fp32 [m, ld])."""
+        self._check_device_sampling()
         if logits.dtype != torch.float32 or logits.device != self.device or logits.dim() != 2 or logits.stride(1) != 1:
             raise _lib.LskError("logits must be a [m, ld] fp32 tensor on the engine device")
         m, ld = logits.shape[0], logits.stride(0)
@@ -560,7 +574,7 @@ class HipEngine:
         point-to-point send / recv go straight from / into the engine's buffers on the current stream."""
         off = ctypes.c_size_t(0)
         self._ck(self.lib.lsk_rows_offset(self._handle, buffer, row_base, ctypes.byref(off)))
-        nbytes = m * self.hidden * 2
+        nbytes = m * self.hidden * self.elem_bytes
         return self._buffers["ws"][off.value: off.value + nbytes].view(self.dtype).view(m, self.hidden)
 
     # ------------------------------------------------------------------ building blocks
@@ -645,12 +659,13 @@ class HipEngine:
     def projection_bytes(self) -> dict:
         hd = self.head_dim
         qdim, kvdim = self.n_heads * hd, self.n_kv_heads * hd
+        eb = self.elem_bytes
         return {
-            "qkv": 2 * (qdim + 2 * kvdim) * self.hidden,
-            "o": 2 * self.hidden * qdim,
-            "gate_up": 2 * 2 * self.intermediate * self.hidden,
-            "down": 2 * self.hidden * self.intermediate,
-            "lm_head": 2 * self.vocab * self.hidden,
+            "qkv": eb * (qdim + 2 * kvdim) * self.hidden,
+            "o": eb * self.hidden * qdim,
+            "gate_up": eb * 2 * self.intermediate * self.hidden,
+            "down": eb * self.hidden * self.intermediate,
+            "lm_head": eb * self.vocab * self.hidden,
         }
 
 

@@ -145,7 +145,8 @@ class HipSelfSpeculativeGenerationStrategy(GenerationStrategy):
         engine.reset()                                            # past_key_values = None
         eos_token_ids = [t for t in eos_token_ids if t is not None]       # a tokenizer without an eos token (reference: `None in list` is just False)
         device_sampled = bool(generation_config.sample and self.device_sampling and not logits_processors
-                              and spec <= _lib.LSK_MAX_SPEC and hasattr(engine, "spec_step_sampled"))
+                              and spec <= _lib.LSK_MAX_SPEC and hasattr(engine, "spec_step_sampled")
+                              and getattr(engine, "samples_on_device", True))
         if device_sampled:
             self._new_sample_stream()
         if (self.fused_generate and not logits_processors and not stopping_criteria and streamer is None
@@ -228,7 +229,7 @@ class HipSelfSpeculativeGenerationStrategy(GenerationStrategy):
         new_ids = [int(t) for t in input_ids[0].tolist()]
         eos_token_ids = [t for t in eos_token_ids if t is not None]
         if (sample and self.device_sampling and not logits_processors and spec <= _lib.LSK_MAX_SPEC
-                and hasattr(engine, "spec_step_sampled")):
+                and hasattr(engine, "spec_step_sampled") and getattr(engine, "samples_on_device", True)):
             # a step called on its own (the reference's tests do) starts a stream; the first step of generate_token_ids continues the one
             # that call drew, so the fused call, the step loop and the layer pipeline consume torch's generator identically
             if self._sample_base is None or (past_key_values is None and not self._stream_fresh):
@@ -371,7 +372,7 @@ class HipAutoRegressiveGenerationStrategy(GenerationStrategy):
         if layer_end > engine.num_layers:
             raise ValueError(f"exit_layer={layer_end} > num_layers={engine.num_layers}")
         device_sampled = bool(generation_config.sample and self.device_sampling and not logits_processors
-                              and hasattr(engine, "ar_step_sampled"))
+                              and hasattr(engine, "ar_step_sampled") and getattr(engine, "samples_on_device", True))
         if device_sampled:
             g = generation_config
             sampling = (float(g.temperature), int(g.top_k), float(g.top_p), int(torch.initial_seed()),

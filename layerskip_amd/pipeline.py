@@ -56,6 +56,8 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
+from . import _lib
+
 BUF_STEP = 0
 BUF_BULK = 1
 BUF_MSG = 2         # row 0 = header (int32 words), rows 1.. = the verify block
@@ -135,6 +137,10 @@ class PipelineSpeculativeDecoder:
 
     def __init__(self, backend, rank: int, world: int, partition: Sequence[Tuple[int, int]], exit_layer: int,
                  group=None, comm_device: Optional[torch.device] = None, optimistic: bool = True):
+        lib = getattr(backend, "lib", None)
+        if lib is not None and lib.lsk_elem_dtype() == _lib.DTYPE_CODES["fp32"]:
+            raise _lib.LskError("the layer pipeline runs bf16 or fp16 engines; this rank's engine computes in fp32 "
+                                "(decode an fp32 model on one GPU, or load it in bf16 / fp16)")
         self.be = backend
         self.rank, self.world = rank, world
         self.partition = list(partition)
