@@ -5,23 +5,9 @@
 #include <new>
 
 #include "lsk_engine.h"
-#include "lsk_launch.h"
 #include "lsk_gemm_big.h"
+#include "lsk_launch.h"
 #include "lsk_small.h"
-
-// ------------------------------------------------------------------------------------------------
-// error plumbing
-// ------------------------------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-
-int lsk_fail(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return 1;
-}
-
 
 extern "C" const char* lsk_last_error(void) { return g_err; }
 extern "C" int lsk_abi_version(void) { return LSK_ABI_VERSION; }
@@ -383,56 +369,25 @@ static int check_rows(lsk_engine* e, int buffer, int row_base, int m) {
     return 0;
 }
 
-static int attn_params(lsk_engine* e, const elem_t* q, elem_t* out, const elem_t* kpool, const elem_t* vpool, int m, int pos_off,
-                       AttnSplitParams& sp, int& pages) {
-    const lsk_config& c = e->cfg;
-    const int hd = c.head_dim;
-    const int qdim = c.n_heads * hd;
-    sp = AttnSplitParams{};
-    sp.q = q; sp.ldq = qdim; sp.kpool = kpool; sp.vpool = vpool; sp.block_table = e->block_table;
-    sp.n_kv = c.n_kv_heads; sp.group = c.n_heads / c.n_kv_heads; sp.M = m; sp.kv_len = &e->state->kv_len; sp.pos_off = pos_off;
-    sp.scale_log2e = (float)((1.0 / sqrt((double)hd)) * 1.4426950408889634);
-    sp.part = e->attn_part; sp.max_pages = e->n_pages;
-    sp.counters = e->fused_attn ? e->attn_cnt : nullptr; sp.out = out; sp.ldo = qdim;
-    const int last_pos = e->kv_len_host + pos_off + m - 1;
-    pages = last_pos / LSK_ATTN_PAGE + 1;
-    if (e->graph_pages > pages) pages = e->graph_pages;    // a captured step launches one page count for all its attention launches
-    if (pages > e->n_pages) return lsk_fail("attention reaches page %d of %d", pages, e->n_pages);
-    sp.n_pages = pages;
-    // query heads of one KV head that share a workgroup (and one fetch of the page): as many as fit the 16 MFMA rows
-    int hw = 1;
-    while (hw * 2 <= sp.group && hw * 2 * m <= LSK_MAX_ROWS && sp.group % (hw * 2) == 0) hw *= 2;
-    sp.heads_per_wg = hw;
-    sp.inv_m = (256 + m - 1) / m;
-    sp.identity_table = e->block_table_identity ? 1 : 0;
-    return 0;
-}
-
+// decode / verify attention of m rows of the step (or prompt) buffer at positions kv_len + pos_off + i
 static int launch_attn(lsk_engine* e, const elem_t* q, elem_t* out, const elem_t* kpool, const elem_t* vpool, int m, int pos_off, hipStream_t st) {
     const lsk_config& c = e->cfg;
-    const int hd = c.head_dim;
-    AttnSplitParams sp;
-    int pages = 0;
-    LSK_TRY(attn_params(e, q, out, kpool, vpool, m, pos_off, sp, pages));
-    const dim3 grid(c.n_heads / sp.heads_per_wg, pages), block(LSK_ATTN_THREADS);
-#ifdef LSK_TRACE
-    sp.trace = lsk_trace_next(1, 0, m, (int)(grid.x * grid.y));
-#endif
+    int pages = (e->kv_len_host + pos_off + m - 1) / LSK_ATTN_PAGE + 1;
+    if (e->graph_pages > pages) pages = e->graph_pages;    // a captured step launches one page count for all its attention launches
+    if (pages > e->n_pages) return lsk_fail("attention reaches page %d of %d", pages, e->n_pages);
     hipEvent_t ea = nullptr, eb = nullptr;
     // algorithmic bytes: K and V of every key in reach, once (GQA: each KV head once)
-    LSK_TRY(profile_pair(e, LSK_PROF_ATTN, m, 2.0 * (double)sizeof(elem_t) * c.n_kv_heads * hd * (double)(e->kv_len_host + pos_off + m), &ea, &eb));
-    const lsk_attn_split_fn kern = lsk_attn_split_for(hd, sp.counters != nullptr);
-    if (ea != nullptr) hipExtLaunchKernelGGL(kern, grid, block, 0, st, ea, eb, 0, LSK_ATTN_HOT_ARGS(sp));
-    else hipLaunchKernelGGL(kern, grid, block, 0, st, LSK_ATTN_HOT_ARGS(sp));
-    HIP_OK(hipGetLastError());
-    if (e->fused_attn) return 0;
-    AttnCombineParams cp{};
-    cp.part = e->attn_part; cp.max_pages = e->n_pages; cp.M = m; cp.kv_len = &e->state->kv_len; cp.pos_off = pos_off;
-    cp.out = out; cp.ldo = c.n_heads * hd;
-    if (hd == 128) hipLaunchKernelGGL((lsk_attn_combine_kernel<128>), dim3(c.n_heads, m), dim3(128), 0, st, cp);
-    else hipLaunchKernelGGL((lsk_attn_combine_kernel<64>), dim3(c.n_heads, m), dim3(64), 0, st, cp);
-    HIP_OK(hipGetLastError());
-    return 0;
+    LSK_TRY(profile_pair(e, LSK_PROF_ATTN, m, 2.0 * (double)sizeof(elem_t) * c.n_kv_heads * c.head_dim * (double)(e->kv_len_host + pos_off + m), &ea, &eb));
+    return launch_attn_decode(c, q, out, kpool, vpool, e->block_table, e->block_table_identity, &e->state->kv_len, pos_off, m, pages,
+                              e->attn_part, e->n_pages, e->fused_attn ? e->attn_cnt : nullptr, st, ea, eb);
+}
+
+// a projection of the decode path with the next profiling event pair (algorithmic bytes: its packed weight)
+template <int PRO, int EPI>
+static int run_gemm(lsk_engine* e, int cat, GemmLaunch<PRO, EPI> g, int target_wgs, hipStream_t st) {
+    hipEvent_t ea = nullptr, eb = nullptr;
+    LSK_TRY(profile_pair(e, cat, g.p.M, (double)g.p.wp_bytes, &ea, &eb));
+    return g.launch(target_wgs, st, nullptr, ea, eb);
 }
 
 // (measurement builds: -DLSK_OPROJ_WGS=128 gives the o_proj launch 128 workgroups of two tiles instead of 256 of one)
@@ -449,53 +404,17 @@ static int launch_attn(lsk_engine* e, const elem_t* q, elem_t* out, const elem_t
 // decoder layers [lb, le) in place over rows of `x` (positions *base_ptr + pos_off + i)
 int lsk_run_layers_dev(lsk_engine* e, elem_t* x, int m, const int* base_ptr, int pos_off, int lb, int le, hipStream_t st) {
     const lsk_config& c = e->cfg;
-    const int qdim = c.n_heads * c.head_dim;
-    const int kvdim = c.n_kv_heads * c.head_dim;
     for (int l = lb; l < le; ++l) {
         const LayerWeights& lw = e->layers[l];
         elem_t* kpool = e->kv_pool + (size_t)l * e->kv_layer_elems;
         elem_t* vpool = kpool + e->kv_half_elems;
-        {   // input RMSNorm -> q/k/v projections -> RoPE -> KV append
-            GemmParams p{};
-            p.x = x; p.ldx = c.hidden; p.M = m; p.K = c.hidden;
-            p.N = qdim + 2 * kvdim; p.n_tiles = p.N / 16;
-            p.wp = lw.wqkv; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * sizeof(elem_t));
-            p.norm_w = lw.norm1; p.eps = c.rms_eps;
-            p.q_out = e->qbuf; p.ldq = qdim; p.kpool = kpool; p.vpool = vpool; p.block_table = e->block_table;
-            p.page_size = c.page_size; p.n_heads = c.n_heads; p.n_kv = c.n_kv_heads; p.head_dim = c.head_dim;
-            p.rope_cos = e->rope_cos; p.rope_sin = e->rope_sin; p.kv_len = base_ptr; p.pos_off = pos_off;
-            hipEvent_t ea = nullptr, eb = nullptr;
-            LSK_TRY(profile_pair(e, LSK_PROF_QKV, m, (double)p.wp_bytes, &ea, &eb));
-            LSK_TRY((launch_gemm<PRO_RMS, EPI_QKV>(p, e->target_wgs, st, nullptr, ea, eb)));
-        }
+        LSK_TRY(run_gemm(e, LSK_PROF_QKV, gemm_qkv(c, x, m, lw.wqkv, lw.norm1, e->rope_cos, e->rope_sin, base_ptr, pos_off, e->block_table,
+                                                   e->qbuf, kpool, vpool), e->target_wgs, st));
         LSK_TRY(launch_attn(e, e->qbuf, e->attn, kpool, vpool, m, pos_off, st));
-        {   // o_proj + residual
-            GemmParams p{};
-            p.x = e->attn; p.ldx = qdim; p.M = m; p.K = qdim; p.N = c.hidden; p.n_tiles = p.N / 16;
-            p.wp = lw.wo; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * sizeof(elem_t));
-            p.h = x; p.ldh = c.hidden;
-            hipEvent_t ea = nullptr, eb = nullptr;
-            LSK_TRY(profile_pair(e, LSK_PROF_OPROJ, m, (double)p.wp_bytes, &ea, &eb));
-            LSK_TRY((launch_gemm<PRO_PLAIN, EPI_RESID>(p, LSK_OPROJ_WGS > 0 ? LSK_OPROJ_WGS : e->target_wgs, st, nullptr, ea, eb)));
-        }
-        {   // post-attention RMSNorm -> gate/up -> SiLU * up
-            GemmParams p{};
-            p.x = x; p.ldx = c.hidden; p.M = m; p.K = c.hidden; p.N = 2 * c.intermediate; p.n_tiles = p.N / 16;
-            p.wp = lw.wgu; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * sizeof(elem_t));
-            p.norm_w = lw.norm2; p.eps = c.rms_eps; p.act = e->act; p.ldact = c.intermediate;
-            hipEvent_t ea = nullptr, eb = nullptr;
-            LSK_TRY(profile_pair(e, LSK_PROF_GATEUP, m, (double)p.wp_bytes, &ea, &eb));
-            LSK_TRY((launch_gemm<PRO_RMS, EPI_SWIGLU>(p, LSK_GATEUP_WGS > 0 ? LSK_GATEUP_WGS : e->target_wgs, st, nullptr, ea, eb)));
-        }
-        {   // down_proj + residual
-            GemmParams p{};
-            p.x = e->act; p.ldx = c.intermediate; p.M = m; p.K = c.intermediate; p.N = c.hidden; p.n_tiles = p.N / 16;
-            p.wp = lw.wdown; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * sizeof(elem_t));
-            p.h = x; p.ldh = c.hidden;
-            hipEvent_t ea = nullptr, eb = nullptr;
-            LSK_TRY(profile_pair(e, LSK_PROF_DOWN, m, (double)p.wp_bytes, &ea, &eb));
-            LSK_TRY((launch_gemm<PRO_PLAIN, EPI_RESID>(p, e->target_wgs, st, nullptr, ea, eb)));
-        }
+        LSK_TRY(run_gemm(e, LSK_PROF_OPROJ, gemm_resid(e->attn, m, c.n_heads * c.head_dim, lw.wo, c.hidden, x),
+                         LSK_OPROJ_WGS > 0 ? LSK_OPROJ_WGS : e->target_wgs, st));
+        LSK_TRY(run_gemm(e, LSK_PROF_GATEUP, gemm_swiglu(c, x, m, lw.wgu, lw.norm2, e->act), LSK_GATEUP_WGS > 0 ? LSK_GATEUP_WGS : e->target_wgs, st));
+        LSK_TRY(run_gemm(e, LSK_PROF_DOWN, gemm_resid(e->act, m, c.intermediate, lw.wdown, c.hidden, x), e->target_wgs, st));
     }
     return 0;
 }
@@ -503,26 +422,15 @@ int lsk_run_layers_dev(lsk_engine* e, elem_t* x, int m, const int* base_ptr, int
 // final norm + lm_head + argmax over rows of x; tokens land in tokens_dev[0..m)
 int lsk_run_head_dev(lsk_engine* e, const elem_t* x, int m, float* logits, int ld_logits, int* tokens_dev, hipStream_t st,
                      elem_t* embed_dst, int kv_add) {
-    const lsk_config& c = e->cfg;
     if (!e->lm_head || !e->final_norm) return lsk_fail("the final norm / lm_head are not bound on this engine (a middle pipeline rank runs no head)");
     if (embed_dst != nullptr && !e->embed) return lsk_fail("the embedding is not bound on this engine");
-    GemmParams p{};
-    p.x = x; p.ldx = c.hidden; p.M = m; p.K = c.hidden; p.N = c.vocab; p.n_tiles = (c.vocab + 15) / 16;
-    p.wp = e->lm_head; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * sizeof(elem_t));
-    p.norm_w = e->final_norm; p.eps = c.rms_eps;
-    p.logits = logits; p.ld_logits = ld_logits; p.part_val = e->part_val; p.part_idx = e->part_idx;
-    int grid = 0;
+    // sample=True (tokens_dev == nullptr): the logits rows are what the caller wants, nobody reads an argmax
+    if (tokens_dev == nullptr && kv_add) return lsk_fail("internal: a head without an argmax launch cannot advance the context");
+    GemmLaunch<PRO_RMS, EPI_HEAD> g = gemm_head(e->cfg, x, m, e->lm_head, e->final_norm, logits, ld_logits, e->part_val, e->part_idx);
     hipEvent_t ea = nullptr, eb = nullptr;
-    LSK_TRY(profile_pair(e, LSK_PROF_HEAD, m, (double)p.wp_bytes, &ea, &eb));
-    LSK_TRY((launch_gemm<PRO_RMS, EPI_HEAD>(p, LSK_HEAD_WGS > 0 ? LSK_HEAD_WGS : e->target_wgs, st, &grid, ea, eb)));
-    if (grid > e->max_parts) return lsk_fail("internal: head grid %d > max_parts %d", grid, e->max_parts);
-    if (tokens_dev == nullptr) {                                 // sample=True: the logits rows are what the caller wants, nobody reads an argmax
-        if (kv_add) return lsk_fail("internal: a head without an argmax launch cannot advance the context");
-        return 0;
-    }
-    hipLaunchKernelGGL(lsk_argmax_finalize_kernel, dim3(m), dim3(embed_dst ? 256 : 64), 0, st, e->part_val, e->part_idx, grid, m, tokens_dev,
-                       e->embed, e->cfg.hidden, e->cfg.vocab, embed_dst, kv_add ? e->state : nullptr, kv_add);
-    HIP_OK(hipGetLastError());
+    LSK_TRY(profile_pair(e, LSK_PROF_HEAD, m, (double)g.p.wp_bytes, &ea, &eb));
+    LSK_TRY(launch_head(g, LSK_HEAD_WGS > 0 ? LSK_HEAD_WGS : e->target_wgs, e->max_parts, tokens_dev, e->embed, embed_dst,
+                        kv_add ? e->state : nullptr, kv_add, st, ea, eb));
     e->kv_len_host += kv_add;
     return 0;
 }
@@ -654,11 +562,7 @@ static int run_bulk_big(lsk_engine* e, int n, int lb, int le, hipStream_t st) {
             LSK_TRY(launch_big_qkv(p, st));
         }
         if (e->flash_prefill) {
-            AttnPrefillParams ap{};
-            ap.q = e->q_bulk; ap.ldq = qdim; ap.out = e->attn_bulk; ap.ldo = qdim; ap.kpool = kpool; ap.vpool = vpool;
-            ap.block_table = e->block_table; ap.n_kv = c.n_kv_heads; ap.group = c.n_heads / c.n_kv_heads; ap.rows = n;
-            ap.kv_len = kvp; ap.pos_off = 0; ap.scale_log2e = (float)((1.0 / sqrt((double)c.head_dim)) * 1.4426950408889634);
-            LSK_TRY(launch_attn_prefill(ap, c.n_heads, c.head_dim, n, st));
+            LSK_TRY(launch_attn_prefill(c, e->q_bulk, e->attn_bulk, kpool, vpool, e->block_table, kvp, 0, n, st));
         } else {
             for (int r0 = 0; r0 < n; r0 += LSK_MAX_ROWS) {
                 const int m = (n - r0) < LSK_MAX_ROWS ? (n - r0) : LSK_MAX_ROWS;
@@ -803,11 +707,7 @@ extern "C" int lsk_time_gateup(lsk_engine* e, int32_t layer, int32_t m, int32_t 
     hipError_t err = hipEventRecord(a, st);
     for (int i = 0; i < iters && rc == 0 && err == hipSuccess; ++i) {
         const LayerWeights& lw = e->layers[(layer + i) % c.num_layers];
-        GemmParams p{};
-        p.x = e->hrow; p.ldx = c.hidden; p.M = m; p.K = c.hidden; p.N = 2 * c.intermediate; p.n_tiles = p.N / 16;
-        p.wp = lw.wgu; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * p.K * sizeof(elem_t));
-        p.norm_w = lw.norm2; p.eps = c.rms_eps; p.act = e->act; p.ldact = c.intermediate;
-        rc = launch_gemm<PRO_RMS, EPI_SWIGLU>(p, e->target_wgs, st);
+        rc = gemm_swiglu(c, e->hrow, m, lw.wgu, lw.norm2, e->act).launch(e->target_wgs, st);
     }
     if (rc == 0 && err == hipSuccess) err = hipEventRecord(b, st);
     if (rc == 0 && err == hipSuccess) err = hipEventSynchronize(b);

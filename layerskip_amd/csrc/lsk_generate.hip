@@ -29,12 +29,6 @@ static int upload_step_inputs(lsk_engine* e, const int32_t* input_ids, int P, co
 // ---- sampling on the device (lsk_sample.h) --------------------------------------------------
 static int sampling_ld(const lsk_config& c) { return (c.vocab + 3) / 4 * 4; }
 
-// RNG tags inside one step (Philox counter word 1): draft row j -> j, verify row r -> 32 + r, acceptance uniforms -> 64,
-// residual draw -> 96.  `offset` (counter words 2-3) must differ between steps: the caller passes a step counter.
-#define LSK_TAG_VERIFY 32
-#define LSK_TAG_ACCEPT 64
-#define LSK_TAG_RESIDUAL 96
-
 // sample=True parameters of one step; nullptr = greedy
 struct StepSampling {
     float temperature;
@@ -156,13 +150,8 @@ static int enqueue_step_body(lsk_engine* e, int P, int S, int E, int n_eos, int 
     if (sm == nullptr) {
         hipLaunchKernelGGL(lsk_accept_kernel, dim3(1), dim3(64), 0, st, e->row_tokens + 1, e->verified, S, e->eos, n_eos, P, e->state, dres);
     } else {
-        AcceptSampledParams ap{};
-        ap.draft = e->row_tokens + 1; ap.verified = e->verified; ap.num_drafts = S; ap.eos = e->eos; ap.n_eos = n_eos; ap.prompt_len = P;
-        ap.p_draft = sm->p_draft; ap.p_verify = sm->p_verify; ap.ld = sm->ld; ap.vocab = c.vocab;
-        ap.seed_lo = (unsigned int)sm->seed; ap.seed_hi = (unsigned int)(sm->seed >> 32);
-        ap.off_lo = (unsigned int)sm->offset; ap.off_hi = (unsigned int)(sm->offset >> 32);
-        ap.tag_accept = LSK_TAG_ACCEPT; ap.tag_residual = LSK_TAG_RESIDUAL; ap.st = e->state; ap.result = dres;
-        hipLaunchKernelGGL(lsk_accept_sampled_kernel, dim3(1), dim3(LSK_SAMPLE_THREADS), 0, st, ap);
+        launch_accept_sampled(e->row_tokens + 1, e->verified, S, e->eos, n_eos, P, sm->p_draft, sm->p_verify, sm->ld, c.vocab, sm->seed,
+                              sm->offset, e->state, dres, st);
     }
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(e->host_result + slot * 64, dres, sizeof(int) * LSK_RES_INTS, hipMemcpyDeviceToHost, st));

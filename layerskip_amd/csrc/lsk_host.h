@@ -13,7 +13,7 @@
 
 #include "lsk_common.h"
 
-// each library defines these once (the message buffer is thread-local)
+// defined once per library, in lsk_launch.h (the message buffer is thread-local)
 int lsk_fail(const char* fmt, ...);
 
 #define HIP_OK(expr)                                                                              \

@@ -30,6 +30,12 @@
 #define LSK_SAMPLE_THREADS 1024
 #define LSK_SAMPLE_WAVES 16
 
+// RNG tags inside one speculation step (Philox counter word 1): draft row j -> j, verify row r -> 32 + r, acceptance uniforms -> 64,
+// residual draw -> 96.  `offset` (counter words 2-3) must differ between steps: the caller passes a step counter.
+#define LSK_TAG_VERIFY 32
+#define LSK_TAG_ACCEPT 64
+#define LSK_TAG_RESIDUAL 96
+
 struct SampleParams {
     const float* logits;        // [m][ld] fp32 (bf16-exact values), device
     int ld;
@@ -958,6 +964,20 @@ __global__ __launch_bounds__(LSK_SAMPLE_THREADS) void lsk_accept_sampled_kernel(
         p.result[3] = kv;
         p.result[LSK_RES_EMIT + n] = next;
     }
+}
+
+// The acceptance of one sampled step (host side): drafts draft[0..num_drafts) with their distributions p_draft against the verify
+// tokens and distributions; state (optional) receives the rollback and the next input token.  The caller checks the launch.
+static inline void launch_accept_sampled(int* draft, int* verified, int num_drafts, const int* eos, int n_eos, int prompt_len,
+                                         const float* p_draft, const float* p_verify, int ld, int vocab, uint64_t seed, uint64_t offset,
+                                         StepState* state, int* result, hipStream_t st) {
+    AcceptSampledParams ap{};
+    ap.draft = draft; ap.verified = verified; ap.num_drafts = num_drafts; ap.eos = eos; ap.n_eos = n_eos; ap.prompt_len = prompt_len;
+    ap.p_draft = p_draft; ap.p_verify = p_verify; ap.ld = ld; ap.vocab = vocab;
+    ap.seed_lo = (unsigned int)seed; ap.seed_hi = (unsigned int)(seed >> 32);
+    ap.off_lo = (unsigned int)offset; ap.off_hi = (unsigned int)(offset >> 32);
+    ap.tag_accept = LSK_TAG_ACCEPT; ap.tag_residual = LSK_TAG_RESIDUAL; ap.st = state; ap.result = result;
+    hipLaunchKernelGGL(lsk_accept_sampled_kernel, dim3(1), dim3(LSK_SAMPLE_THREADS), 0, st, ap);
 }
 
 // ---- sample=True on the layer pipeline (SURVEY 8e x 8f N2) -----------------------------------------------------------------------
