@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LSK_ABI_VERSION 5   /* 2: options 4 / 6 removed, draft-block / sampled / profile-table entry points added, lsk_test_* moved to
+#define LSK_ABI_VERSION 6   /* 2: options 4 / 6 removed, draft-block / sampled / profile-table entry points added, lsk_test_* moved to
                              liblayerskip_hip_test.so (include/layerskip_hip_test.h), lsk_engine_weights_checksum added
                              3: sample=True on the layer pipeline (lsk_draft_block_sampled, lsk_pipeline_pack_sampled,
                              lsk_pipeline_tail_sampled, lsk_pipeline_residual, lsk_pipeline_result_words); message header 24 -> 40 words;
@@ -41,7 +41,9 @@ extern "C" {
                              lsk_engine_set_globals accepts NULL embed / final_norm / lm_head (middle pipeline ranks)
                              4: LSK_MAX_EOS 8 -> 1024 (the reference folds any number of stop_token_ids into the eos list, generator_base.py:106;
                              the workspace's eos region grew with it); vocabularies that are not a multiple of 16 documented as supported
-                             5: sample=True autoregressive decoding on the device (lsk_ar_generate_sampled, lsk_ar_step_sampled) */
+                             5: sample=True autoregressive decoding on the device (lsk_ar_generate_sampled, lsk_ar_step_sampled)
+                             6: opt-in FP8 (e4m3) weight storage (lsk_packed_bytes_fp8, lsk_pack_linear_fp8, lsk_engine_set_weight_format,
+                             lsk_engine_set_layer_prefill) */
 #define LSK_MAX_ROWS 16
 #define LSK_MAX_SPEC 15   /* num_speculations handled by one fused step (rows = spec + 1) */
 #define LSK_MAX_EOS 1024   /* eos + stop token ids of one generation (generator_base.py:106); ids outside the vocabulary are dropped by the host */
@@ -106,6 +108,20 @@ int lsk_pack_linear(const void* src, int32_t n_rows, int32_t k, int32_t ld_src, 
                     int32_t dst_tile_offset, int32_t dst_tile_stride, int32_t rope_head_dim,
                     void* stream);
 
+/* ---- FP8 (OCP e4m3fn) weight storage, opt-in, bf16 library only (the fp16 / fp32 libraries export the symbols and return an error) ----
+ * Format (specification: layerskip_amd/quant.py, which lsk_pack_linear_fp8 agrees with bit for bit): per output row one power of two
+ * 2^k -- k the smallest exponent with amax_row <= 448 * 2^k; 0 for an all-zero row; >= -117 -- and codes = e4m3fn(w / 2^k), round to
+ * nearest even.  code * 2^k is exactly representable in bf16 and a power of two commutes with every fp32 rounding of the accumulation,
+ * so an engine on FP8 buffers computes BIT FOR BIT what the bf16 engine computes on the dequantised weights.
+ * Buffer of n_rows x k: the tiles of lsk_pack_linear with 1-byte elements (16 * ceil(n_rows / 16) * k bytes; a tile's k-step is 512 B,
+ * a lane's fragment 8 B), then one fp32 2^k per PACKED row (the q/k RoPE permutation, the gate/up interleave and the q|k|v
+ * concatenation apply to the scales as to the tiles; padded rows of a ragged last tile: code 0, scale 1).
+ * lsk_pack_linear_fp8 takes lsk_pack_linear's arguments plus `dst_rows`, the rows of the WHOLE destination buffer (a multiple of 16;
+ * it locates the scale table behind the codes when several sources share one buffer). */
+int lsk_packed_bytes_fp8(int32_t n_rows, int32_t k, size_t* out_bytes);
+int lsk_pack_linear_fp8(const void* src, int32_t n_rows, int32_t k, int32_t ld_src, void* dst, int32_t dst_rows,
+                        int32_t dst_tile_offset, int32_t dst_tile_stride, int32_t rope_head_dim, void* stream);
+
 /* ---- engine lifetime ---------------------------------------------------------------------- */
 int lsk_engine_create(const lsk_config* cfg, void* workspace, size_t workspace_bytes,
                       void* kv_pool, size_t kv_pool_bytes, lsk_engine** out);
@@ -119,6 +135,17 @@ int lsk_engine_destroy(lsk_engine* e);
  * norm1 / norm2 are the plain bf16 RMSNorm gains (input_layernorm / post_attention_layernorm). */
 int lsk_engine_set_layer(lsk_engine* e, int32_t layer, const void* wqkv, const void* wo,
                          const void* wgu, const void* wdown, const void* norm1, const void* norm2);
+/* Format of the packed projection buffers (wqkv / wo / wgu / wdown of every layer and lm_head) this engine is handed: one format per
+ * engine, set before the first lsk_engine_set_layer.  A setter and not a field of lsk_config: the struct is passed by value-layout
+ * across three libraries and the kernel-test library, and every existing caller constructs it positionally; a call the default
+ * path never makes cannot change it.  LSK_WEIGHT_FORMAT_FP8_E4M3: the decode-path kernels (lsk_run_layers, lsk_run_head, the fused
+ * steps) read ONLY the FP8 buffers; the MFMA-tiled prefill kernels (lsk_run_bulk from LSK_OPT_BIG_THRESHOLD rows on) read model-dtype
+ * packed copies of the DEQUANTISED projections bound with lsk_engine_set_layer_prefill (lsk_pack_linear of quant.dequantize_rows):
+ * same values, so prompt KV and exit hiddens are those of the bf16 engine on the dequantised model; packed bytes are 1.5 x bf16's. */
+#define LSK_WEIGHT_FORMAT_ELEM 0       /* model dtype (default) */
+#define LSK_WEIGHT_FORMAT_FP8_E4M3 1
+int lsk_engine_set_weight_format(lsk_engine* e, int32_t weight_format);
+int lsk_engine_set_layer_prefill(lsk_engine* e, int32_t layer, const void* wqkv, const void* wo, const void* wgu, const void* wdown);
 /* embed: plain bf16 [V][H]; final_norm: bf16 [H]; lm_head: PACKED [V][H] -- each may be NULL on a pipeline rank that never embeds a
  * token / runs a head (a middle rank: checkpoint.load_layer_range(embed=False, head=False)); the entry points that need them say so;
  * rope_cos / rope_sin: bf16 [rope_len][head_dim/2] (host-precomputed exactly as
@@ -335,8 +362,8 @@ int lsk_engine_set_profile(lsk_engine* e, int32_t enable);
 int lsk_engine_get_profile(lsk_engine* e, float* total_ms, int32_t* launches);
 /* The same for EVERY kernel class of the decode path: q/k/v (0), attention (1), o_proj (2), gate/up (3), down (4),
  * lm_head (5), each split into 1-row (draft) and multi-row (verify) passes: arrays of 12 entries, index =
- * 2 * class + (rows > 1): summed duration (ms), launches, summed ALGORITHMIC bytes (packed weights once; K and V of the
- * keys in reach once for attention).  Clears the log. */
+ * 2 * class + (rows > 1): summed duration (ms), launches, summed ALGORITHMIC bytes (packed weights once, in the format the
+ * launch reads: FP8 codes + scales under LSK_WEIGHT_FORMAT_FP8_E4M3; K and V of the keys in reach once for attention).  Clears the log. */
 #define LSK_PROF_ENTRIES 12
 int lsk_engine_get_profile_table(lsk_engine* e, int32_t n_entries, float* ms, int32_t* launches, double* bytes);
 

@@ -12,12 +12,13 @@ from ctypes import POINTER, c_char_p, c_float, c_int32, c_size_t, c_uint64, c_vo
 LSK_MAX_ROWS = 16
 LSK_MAX_SPEC = 15
 LSK_MAX_EOS = 1024
-LSK_ABI_VERSION = 5
+LSK_ABI_VERSION = 6
 LSK_OPT_BIG_THRESHOLD = 1
 LSK_OPT_TARGET_WGS = 2
 LSK_OPT_FUSED_ATTN = 3
 LSK_OPT_FLASH_PREFILL = 5
 LSK_OPT_GRAPH_STEPS = 7       # steady-state greedy steps replayed from hipGraphs (default off)
+WEIGHT_FORMATS = {"bf16": 0, "fp8_e4m3": 1}    # HipEngine(weight_format=...) -> LSK_WEIGHT_FORMAT_* ("bf16": the model dtype, the default)
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(_CSRC, "liblayerskip_hip.so")            # bf16 build (BASELINE configs)
@@ -54,6 +55,10 @@ PROTOTYPES = {
     "lsk_kv_pool_bytes": (c_int32, [POINTER(LskConfig), POINTER(c_size_t)]),
     "lsk_packed_bytes": (c_int32, [c_int32, c_int32, POINTER(c_size_t)]),
     "lsk_pack_linear": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "lsk_packed_bytes_fp8": (c_int32, [c_int32, c_int32, POINTER(c_size_t)]),
+    "lsk_pack_linear_fp8": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "lsk_engine_set_weight_format": (c_int32, [c_void_p, c_int32]),
+    "lsk_engine_set_layer_prefill": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsk_engine_create": (c_int32, [POINTER(LskConfig), c_void_p, c_size_t, c_void_p, c_size_t, POINTER(c_void_p)]),
     "lsk_engine_destroy": (c_int32, [c_void_p]),
     "lsk_engine_set_layer": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -32,6 +32,7 @@ class SyntheticArguments:
     prompt_len: int = 512
     device: str = "cuda:0"
     pp_balance: str = "draft"          # multi-GPU (torchrun) layer split: "draft" | "memory" (layerskip_amd.pipeline.plan_partition)
+    weight_format: str = "bf16"        # "fp8_e4m3": projections stored as e4m3 codes + one power of two per row (layerskip_amd/quant.py)
 
 
 def setup(args: Arguments, syn: SyntheticArguments):
@@ -96,17 +97,20 @@ def load_model_and_tokenizer(args: Arguments, syn: SyntheticArguments, exit_laye
     return model, tokenizer
 
 
-def make_strategy(cfg: GenerationConfig, ctx=None, partition=None, backend_factory=None):
+def make_strategy(cfg: GenerationConfig, ctx=None, partition=None, backend_factory=None, weight_format: str = "bf16"):
     name = cfg.generation_strategy.replace("_hip", "")
+    # (the default format passes no keyword: the engines are built exactly as before)
+    engine_kwargs = {"weight_format": weight_format} if weight_format != "bf16" else None
     if ctx is not None:
         from ..pipeline_strategy import PIPELINE_STRATEGIES
         if name not in PIPELINE_STRATEGIES:
             raise ValueError(f"Unsupported generation strategy: {cfg.generation_strategy}")
-        return PIPELINE_STRATEGIES[name](ctx, partition, backend_factory=backend_factory)
+        # every rank's engine gets the keyword (the pipeline forwards engine_kwargs to its backend factory)
+        return PIPELINE_STRATEGIES[name](ctx, partition, backend_factory=backend_factory, engine_kwargs=engine_kwargs)
     from ..hip_strategies import STRATEGIES
     if name not in STRATEGIES:
         raise ValueError(f"Unsupported generation strategy: {cfg.generation_strategy}")
-    return STRATEGIES[name]()
+    return STRATEGIES[name](engine_kwargs=engine_kwargs)
 
 
 def run_on_rank0(ctx, strategy, model, fn):

@@ -9,6 +9,8 @@
 
 struct LayerWeights {
     const elem_t *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wdown = nullptr, *norm1 = nullptr, *norm2 = nullptr;
+    // FP8 weight format: model-dtype packed copies of the DEQUANTISED projections, read by the prefill kernels alone (lsk_engine_set_layer_prefill)
+    const elem_t *pf_wqkv = nullptr, *pf_wo = nullptr, *pf_wgu = nullptr, *pf_wdown = nullptr;
 };
 
 struct lsk_engine {
@@ -16,6 +18,7 @@ struct lsk_engine {
     std::vector<LayerWeights> layers;
     const elem_t *embed = nullptr, *final_norm = nullptr, *lm_head = nullptr, *rope_cos = nullptr, *rope_sin = nullptr;
     int rope_len = 0;
+    int weight_format = 0;        // LSK_WEIGHT_FORMAT_*: what wqkv / wo / wgu / wdown / lm_head point at (lsk_engine_set_weight_format)
     // device workspace carve
     unsigned char* ws = nullptr;
     size_t ws_bytes = 0;

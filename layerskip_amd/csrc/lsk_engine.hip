@@ -123,6 +123,33 @@ extern "C" int lsk_pack_linear(const void* src, int32_t n_rows, int32_t k, int32
     return 0;
 }
 
+extern "C" int lsk_packed_bytes_fp8(int32_t n_rows, int32_t k, size_t* out_bytes) {
+    if (!out_bytes) return lsk_fail("lsk_packed_bytes_fp8: null out");
+    if (n_rows <= 0 || k <= 0 || (k % 32)) return lsk_fail("lsk_packed_bytes_fp8: n_rows=%d k=%d (k must be a multiple of 32)", n_rows, k);
+    const size_t rows = (size_t)((n_rows + 15) / 16) * 16;
+    *out_bytes = rows * (size_t)k + rows * sizeof(float);       // codes, then one fp32 power of two per packed row
+    return 0;
+}
+
+extern "C" int lsk_pack_linear_fp8(const void* src, int32_t n_rows, int32_t k, int32_t ld_src, void* dst, int32_t dst_rows,
+                                   int32_t dst_tile_offset, int32_t dst_tile_stride, int32_t rope_head_dim, void* stream) {
+#if LSK_ELEM_DTYPE == 0
+    if (!src || !dst) return lsk_fail("lsk_pack_linear_fp8: null pointer");
+    if (n_rows <= 0 || k <= 0 || (k % 32)) return lsk_fail("lsk_pack_linear_fp8: k=%d must be a positive multiple of 32", k);
+    if (rope_head_dim > 0 && ((rope_head_dim % 32) || (n_rows % rope_head_dim))) return lsk_fail("lsk_pack_linear_fp8: bad rope_head_dim");
+    const int n_tiles = (n_rows + 15) / 16;
+    if (dst_rows <= 0 || (dst_rows % 16) || dst_tile_offset < 0 || dst_tile_stride < 1 ||
+        (long long)dst_tile_offset + (long long)(n_tiles - 1) * dst_tile_stride >= dst_rows / 16)
+        return lsk_fail("lsk_pack_linear_fp8: tiles %d + %d x %d do not fit a destination of %d rows", dst_tile_offset, n_tiles, dst_tile_stride, dst_rows);
+    hipLaunchKernelGGL(lsk_pack_fp8_kernel, dim3((unsigned)n_tiles * 16), dim3(256), 0, (hipStream_t)stream, (const elem_t*)src, n_rows, k,
+                       ld_src, (unsigned char*)dst, dst_rows, dst_tile_offset, dst_tile_stride, rope_head_dim);
+    HIP_OK(hipGetLastError());
+    return 0;
+#else
+    return lsk_fail("lsk_pack_linear_fp8: FP8 weight storage exists in the bf16 library only");
+#endif
+}
+
 extern "C" int lsk_engine_destroy(lsk_engine* e);
 
 extern "C" int lsk_engine_create(const lsk_config* cfg, void* workspace, size_t workspace_bytes, void* kv_pool, size_t kv_pool_bytes,
@@ -215,6 +242,29 @@ extern "C" int lsk_engine_set_layer(lsk_engine* e, int32_t layer, const void* wq
     LayerWeights& lw = e->layers[layer];
     lw.wqkv = (const elem_t*)wqkv; lw.wo = (const elem_t*)wo; lw.wgu = (const elem_t*)wgu; lw.wdown = (const elem_t*)wdown;
     lw.norm1 = (const elem_t*)norm1; lw.norm2 = (const elem_t*)norm2;
+    return 0;
+}
+
+extern "C" int lsk_engine_set_weight_format(lsk_engine* e, int32_t weight_format) {
+    if (!e) return lsk_fail("lsk_engine_set_weight_format: null engine");
+    if (weight_format != LSK_WEIGHT_FORMAT_ELEM && weight_format != LSK_WEIGHT_FORMAT_FP8_E4M3)
+        return lsk_fail("lsk_engine_set_weight_format: unknown weight format %d", weight_format);
+#if LSK_ELEM_DTYPE != 0
+    if (weight_format != LSK_WEIGHT_FORMAT_ELEM) return lsk_fail("lsk_engine_set_weight_format: FP8 weight storage exists in the bf16 library only");
+#endif
+    if (weight_format != e->weight_format) {                    // captured steps carry the kernel instances of the old format
+        for (auto& g : e->graphs) (void)hipGraphExecDestroy(g.exec);
+        e->graphs.clear();
+    }
+    e->weight_format = weight_format;
+    return 0;
+}
+
+extern "C" int lsk_engine_set_layer_prefill(lsk_engine* e, int32_t layer, const void* wqkv, const void* wo, const void* wgu, const void* wdown) {
+    if (!e || layer < 0 || layer >= e->cfg.num_layers) return lsk_fail("lsk_engine_set_layer_prefill: bad layer %d", layer);
+    if (!wqkv || !wo || !wgu || !wdown) return lsk_fail("lsk_engine_set_layer_prefill: null weight");
+    LayerWeights& lw = e->layers[layer];
+    lw.pf_wqkv = (const elem_t*)wqkv; lw.pf_wo = (const elem_t*)wo; lw.pf_wgu = (const elem_t*)wgu; lw.pf_wdown = (const elem_t*)wdown;
     return 0;
 }
 
@@ -382,11 +432,16 @@ static int launch_attn(lsk_engine* e, const elem_t* q, elem_t* out, const elem_t
                               e->attn_part, e->n_pages, e->fused_attn ? e->attn_cnt : nullptr, st, ea, eb);
 }
 
+// bytes a projection launch streams: its packed weight (FP8 format: the codes and the rows' powers of two)
+static double gemm_stream_bytes(const GemmParams& p) {
+    return (double)p.wp_bytes + (p.wfmt == LSK_WF_FP8 ? (double)p.n_tiles * 16 * sizeof(float) : 0.0);
+}
+
 // a projection of the decode path with the next profiling event pair (algorithmic bytes: its packed weight)
 template <int PRO, int EPI>
 static int run_gemm(lsk_engine* e, int cat, GemmLaunch<PRO, EPI> g, int target_wgs, hipStream_t st) {
     hipEvent_t ea = nullptr, eb = nullptr;
-    LSK_TRY(profile_pair(e, cat, g.p.M, (double)g.p.wp_bytes, &ea, &eb));
+    LSK_TRY(profile_pair(e, cat, g.p.M, gemm_stream_bytes(g.p), &ea, &eb));
     return g.launch(target_wgs, st, nullptr, ea, eb);
 }
 
@@ -404,17 +459,18 @@ static int run_gemm(lsk_engine* e, int cat, GemmLaunch<PRO, EPI> g, int target_w
 // decoder layers [lb, le) in place over rows of `x` (positions *base_ptr + pos_off + i)
 int lsk_run_layers_dev(lsk_engine* e, elem_t* x, int m, const int* base_ptr, int pos_off, int lb, int le, hipStream_t st) {
     const lsk_config& c = e->cfg;
+    const int wf = e->weight_format;
     for (int l = lb; l < le; ++l) {
         const LayerWeights& lw = e->layers[l];
         elem_t* kpool = e->kv_pool + (size_t)l * e->kv_layer_elems;
         elem_t* vpool = kpool + e->kv_half_elems;
         LSK_TRY(run_gemm(e, LSK_PROF_QKV, gemm_qkv(c, x, m, lw.wqkv, lw.norm1, e->rope_cos, e->rope_sin, base_ptr, pos_off, e->block_table,
-                                                   e->qbuf, kpool, vpool), e->target_wgs, st));
+                                                   e->qbuf, kpool, vpool, wf), e->target_wgs, st));
         LSK_TRY(launch_attn(e, e->qbuf, e->attn, kpool, vpool, m, pos_off, st));
-        LSK_TRY(run_gemm(e, LSK_PROF_OPROJ, gemm_resid(e->attn, m, c.n_heads * c.head_dim, lw.wo, c.hidden, x),
+        LSK_TRY(run_gemm(e, LSK_PROF_OPROJ, gemm_resid(e->attn, m, c.n_heads * c.head_dim, lw.wo, c.hidden, x, wf),
                          LSK_OPROJ_WGS > 0 ? LSK_OPROJ_WGS : e->target_wgs, st));
-        LSK_TRY(run_gemm(e, LSK_PROF_GATEUP, gemm_swiglu(c, x, m, lw.wgu, lw.norm2, e->act), LSK_GATEUP_WGS > 0 ? LSK_GATEUP_WGS : e->target_wgs, st));
-        LSK_TRY(run_gemm(e, LSK_PROF_DOWN, gemm_resid(e->act, m, c.intermediate, lw.wdown, c.hidden, x), e->target_wgs, st));
+        LSK_TRY(run_gemm(e, LSK_PROF_GATEUP, gemm_swiglu(c, x, m, lw.wgu, lw.norm2, e->act, wf), LSK_GATEUP_WGS > 0 ? LSK_GATEUP_WGS : e->target_wgs, st));
+        LSK_TRY(run_gemm(e, LSK_PROF_DOWN, gemm_resid(e->act, m, c.intermediate, lw.wdown, c.hidden, x, wf), e->target_wgs, st));
     }
     return 0;
 }
@@ -426,9 +482,9 @@ int lsk_run_head_dev(lsk_engine* e, const elem_t* x, int m, float* logits, int l
     if (embed_dst != nullptr && !e->embed) return lsk_fail("the embedding is not bound on this engine");
     // sample=True (tokens_dev == nullptr): the logits rows are what the caller wants, nobody reads an argmax
     if (tokens_dev == nullptr && kv_add) return lsk_fail("internal: a head without an argmax launch cannot advance the context");
-    GemmLaunch<PRO_RMS, EPI_HEAD> g = gemm_head(e->cfg, x, m, e->lm_head, e->final_norm, logits, ld_logits, e->part_val, e->part_idx);
+    GemmLaunch<PRO_RMS, EPI_HEAD> g = gemm_head(e->cfg, x, m, e->lm_head, e->final_norm, logits, ld_logits, e->part_val, e->part_idx, e->weight_format);
     hipEvent_t ea = nullptr, eb = nullptr;
-    LSK_TRY(profile_pair(e, LSK_PROF_HEAD, m, (double)g.p.wp_bytes, &ea, &eb));
+    LSK_TRY(profile_pair(e, LSK_PROF_HEAD, m, gemm_stream_bytes(g.p), &ea, &eb));
     LSK_TRY(launch_head(g, LSK_HEAD_WGS > 0 ? LSK_HEAD_WGS : e->target_wgs, e->max_parts, tokens_dev, e->embed, embed_dst,
                         kv_add ? e->state : nullptr, kv_add, st, ea, eb));
     e->kv_len_host += kv_add;
@@ -547,6 +603,11 @@ static int run_bulk_big(lsk_engine* e, int n, int lb, int le, hipStream_t st) {
     const int qdim = c.n_heads * c.head_dim;
     const int kvdim = c.n_kv_heads * c.head_dim;
     const int* kvp = &e->state->kv_len;
+    // FP8 weight format: the prefill kernels read the model-dtype packed copies of the dequantised projections
+    const bool pf = e->weight_format != LSK_WEIGHT_FORMAT_ELEM;
+    if (pf)
+        for (int l = lb; l < le; ++l)
+            if (!e->layers[l].pf_wqkv) return lsk_fail("layer %d: no prefill weights bound (lsk_engine_set_layer_prefill)", l);
     for (int l = lb; l < le; ++l) {
         const LayerWeights& lw = e->layers[l];
         elem_t* kpool = e->kv_pool + (size_t)l * e->kv_layer_elems;
@@ -555,7 +616,7 @@ static int run_bulk_big(lsk_engine* e, int n, int lb, int le, hipStream_t st) {
         HIP_OK(hipGetLastError());
         {
             BigGemmParams p{};
-            p.x = e->xn_bulk; p.ldx = c.hidden; p.M = n; p.K = c.hidden; p.wp = lw.wqkv; p.N = qdim + 2 * kvdim; p.n_tiles = p.N / 16;
+            p.x = e->xn_bulk; p.ldx = c.hidden; p.M = n; p.K = c.hidden; p.wp = pf ? lw.pf_wqkv : lw.wqkv; p.N = qdim + 2 * kvdim; p.n_tiles = p.N / 16;
             p.q_out = e->q_bulk; p.ldq = qdim; p.kpool = kpool; p.vpool = vpool; p.block_table = e->block_table; p.page_size = c.page_size;
             p.n_heads = c.n_heads; p.n_kv = c.n_kv_heads; p.head_dim = c.head_dim; p.rope_cos = e->rope_cos; p.rope_sin = e->rope_sin;
             p.kv_len = kvp; p.pos_off = 0;
@@ -571,7 +632,7 @@ static int run_bulk_big(lsk_engine* e, int n, int lb, int le, hipStream_t st) {
         }
         {
             BigGemmParams p{};
-            p.x = e->attn_bulk; p.ldx = qdim; p.M = n; p.K = qdim; p.wp = lw.wo; p.N = c.hidden; p.n_tiles = p.N / 16;
+            p.x = e->attn_bulk; p.ldx = qdim; p.M = n; p.K = qdim; p.wp = pf ? lw.pf_wo : lw.wo; p.N = c.hidden; p.n_tiles = p.N / 16;
             p.h = e->hbulk; p.ldh = c.hidden;
             LSK_TRY(launch_big_resid(p, st));
         }
@@ -579,13 +640,13 @@ static int run_bulk_big(lsk_engine* e, int n, int lb, int le, hipStream_t st) {
         HIP_OK(hipGetLastError());
         {
             BigGemmParams p{};
-            p.x = e->xn_bulk; p.ldx = c.hidden; p.M = n; p.K = c.hidden; p.wp = lw.wgu; p.N = 2 * c.intermediate; p.n_tiles = p.N / 16;
+            p.x = e->xn_bulk; p.ldx = c.hidden; p.M = n; p.K = c.hidden; p.wp = pf ? lw.pf_wgu : lw.wgu; p.N = 2 * c.intermediate; p.n_tiles = p.N / 16;
             p.act = e->act_bulk; p.ldact = c.intermediate;
             LSK_TRY(launch_big_gateup(p, st));
         }
         {
             BigGemmParams p{};
-            p.x = e->act_bulk; p.ldx = c.intermediate; p.M = n; p.K = c.intermediate; p.wp = lw.wdown; p.N = c.hidden; p.n_tiles = p.N / 16;
+            p.x = e->act_bulk; p.ldx = c.intermediate; p.M = n; p.K = c.intermediate; p.wp = pf ? lw.pf_wdown : lw.wdown; p.N = c.hidden; p.n_tiles = p.N / 16;
             p.h = e->hbulk; p.ldh = c.hidden;
             LSK_TRY(launch_big_resid(p, st));
         }
@@ -707,7 +768,7 @@ extern "C" int lsk_time_gateup(lsk_engine* e, int32_t layer, int32_t m, int32_t 
     hipError_t err = hipEventRecord(a, st);
     for (int i = 0; i < iters && rc == 0 && err == hipSuccess; ++i) {
         const LayerWeights& lw = e->layers[(layer + i) % c.num_layers];
-        rc = gemm_swiglu(c, e->hrow, m, lw.wgu, lw.norm2, e->act).launch(e->target_wgs, st);
+        rc = gemm_swiglu(c, e->hrow, m, lw.wgu, lw.norm2, e->act, e->weight_format).launch(e->target_wgs, st);
     }
     if (rc == 0 && err == hipSuccess) err = hipEventRecord(b, st);
     if (rc == 0 && err == hipSuccess) err = hipEventSynchronize(b);

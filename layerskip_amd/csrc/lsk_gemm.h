@@ -49,7 +49,8 @@ struct UnitInfo {
     int steps_c;     // k-steps of the chunk
 };
 
-template <int NW>
+// WB: bytes per packed weight element (LSK_EB in the model-dtype format, 1 in the FP8 format)
+template <int NW, int WB = LSK_EB>
 __device__ __forceinline__ UnitInfo lsk_unit_info(int u, int units, int ntl, int ksteps, int tile0, int w, int lane) {
     constexpr int WAVES = NW, KC_STEPS = NW * LSK_SPW;
     UnitInfo r;
@@ -61,7 +62,7 @@ __device__ __forceinline__ UnitInfo lsk_unit_info(int u, int units, int ntl, int
     const int ks0 = w * spw;
     r.c = c; r.tl = tl; r.ks0 = ks0; r.steps_c = steps_c;
     r.nvalid = max(0, min(spw, steps_c - ks0));
-    r.off0 = ((unsigned)(tile0 + tl) * (unsigned)ksteps + (unsigned)(c * KC_STEPS + ks0)) * (unsigned)(512 * LSK_EB) + (unsigned)lane * (unsigned)(8 * LSK_EB);
+    r.off0 = ((unsigned)(tile0 + tl) * (unsigned)ksteps + (unsigned)(c * KC_STEPS + ks0)) * (unsigned)(512 * WB) + (unsigned)lane * (unsigned)(8 * WB);
     return r;
 }
 
@@ -88,6 +89,45 @@ __device__ __forceinline__ elem8 lsk_ring_frag(const u32x4 (&ring)[LSK_SPW * LSK
     return __builtin_bit_cast(elem8, __builtin_shufflevector(ring[2 * s], ring[2 * s + 1], 0, 1, 2, 3, 4, 5, 6, 7));
 #endif
 }
+
+// ---- weight formats ------------------------------------------------------------------------------------------------------------
+// LSK_WF_ELEM: the packed weights are model-dtype elements (everything above).  LSK_WF_FP8 (bf16 build only, opt-in): OCP e4m3fn codes
+// in the same 16(n) x 32(k) fragment-major tile order with 1-byte elements -- a k-step of a tile is 512 B, a lane's fragment 8 B, one
+// raw_buffer_load_b64 per ring slot -- followed by one fp32 power of two per PACKED row (lsk_pack_fp8_kernel, lsk_small.h).  The codes
+// are widened to bf16 at consumption (exact: 3 mantissa bits into 7) and go through the SAME MFMA in the SAME order as the bf16 format;
+// the row's power of two multiplies the reduced fp32 tile once, in front of the epilogue's first rounding.  A power of two commutes
+// with every fp32 rounding of the accumulation, so the result is bit for bit the bf16 kernel's on the dequantised weights.
+enum { LSK_WF_ELEM = 0, LSK_WF_FP8 = 1 };
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+template <int WF> struct lsk_wfmt { typedef u32x4 slot_t; static constexpr int SLOTS = LSK_SPW * LSK_LPF, WB = LSK_EB; };
+template <> struct lsk_wfmt<LSK_WF_FP8> { typedef u32x2 slot_t; static constexpr int SLOTS = LSK_SPW, WB = 1; };
+
+#define lsk_ring_fill_fp8(ring, s, rsrc, u, valid) do { \
+        const unsigned lsk_off = (valid) ? (u).off0 + (unsigned)(s) * 512u : LSK_OOB_OFFSET; \
+        (ring)[s] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, lsk_off, 0, 2 /* nt */); \
+    } while (0)
+// (inside a template on WF: the branch not taken is never instantiated, so each form only sees its own slot type)
+#define lsk_ring_fill_wf(WF, ring, s, rsrc, u, valid) do { \
+        if constexpr ((WF) == LSK_WF_FP8) lsk_ring_fill_fp8(ring, s, rsrc, u, valid); else lsk_ring_fill(ring, s, rsrc, u, valid); \
+    } while (0)
+#if LSK_ELEM_DTYPE == 0
+// 8 e4m3 codes -> 8 bf16: v_cvt_pk_f32_fp8 (OCP on gfx950) gives two fp32 whose low 16 bits are zero, so the bf16 is the high half --
+// no rounding, one v_perm_b32 per pair
+typedef float lsk_f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned lsk_fp8x2_to_bf16x2(unsigned codes, bool hi) {
+    const lsk_f32x2 f = hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)codes, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)codes, false);
+    // (the elements go through scalars first: __builtin_bit_cast applied to a vector-element expression reads element 0 whatever the index)
+    const float f0 = f[0], f1 = f[1];
+    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, f1), __builtin_bit_cast(unsigned, f0), 0x07060302u);
+}
+__device__ __forceinline__ elem8 lsk_ring_frag(const u32x2 (&ring)[LSK_SPW], int s) {
+    const u32x2 c = ring[s];
+    u32x4 o;
+    o[0] = lsk_fp8x2_to_bf16x2(c[0], false); o[1] = lsk_fp8x2_to_bf16x2(c[0], true);
+    o[2] = lsk_fp8x2_to_bf16x2(c[1], false); o[3] = lsk_fp8x2_to_bf16x2(c[1], true);
+    return __builtin_bit_cast(elem8, o);
+}
+#endif
 
 // ---- workgroup geometry: NW waves split the k-steps of a K-chunk of NW x 16 x 32 features, 16 k-steps (= the ring depth) per wave ----
 // 8 waves / 4096-feature chunks are the shape of rounds 1-5.  Round 6 (profiles/r06_ab_1B_options.json,
@@ -207,7 +247,7 @@ __device__ __forceinline__ void lsk_head_tile(const GemmParams& p, const f32x4& 
     }
 }
 
-template <int PRO, int EPI, int MB, int NW>
+template <int PRO, int EPI, int MB, int NW, int WF = LSK_WF_ELEM>
 __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParams& p, const int block_id, unsigned char* smem) {
     constexpr int WAVES = NW, THREADS = NW * 64, KC_STEPS = NW * LSK_SPW;        // the workgroup's geometry (lsk_gemm_waves): 8 or 4 waves
     // q/k/v: the verified context length is read FIRST (its pointer is a preloaded argument): the answer is back when the ring has
@@ -262,15 +302,27 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
 #pragma unroll
         for (int i = 0; i < 4; ++i) pre_a[i] = hp.h[(size_t)min(rg * 4 + i, M - 1) * hp.ldh + n];
     }
+    // FP8 weights: the power of two of this lane's column of the wave's tile(s), one fp32 per packed row behind the codes (the table
+    // covers the padded rows of a ragged last tile, so a clamped TILE index is always valid).  Addresses from preloaded arguments only:
+    // out in front of the rows and the ring, like the residual values.  sc0: the wave's tile (SWIGLU: its gate tile), sc1: its up tile,
+    // scu: the tile of the current unit of a one-chunk lm_head (tile tl belongs to wave tl % WAVES; fetched one unit ahead in the loop).
+    [[maybe_unused]] float sc0, sc1, scu;
+    if constexpr (WF == LSK_WF_FP8) {
+        const float* wscale = (const float*)((const unsigned char*)hp.wp + hp.wp_bytes);
+        const int t0 = (EPI == EPI_SWIGLU) ? tile0 + 2 * w : tile0 + w;
+        sc0 = wscale[min(t0, hp.n_tiles - 1) * 16 + c16];
+        if (EPI == EPI_SWIGLU) sc1 = wscale[min(t0 + 1, hp.n_tiles - 1) * 16 + c16];
+        if (EPI == EPI_HEAD) scu = wscale[tile0 * 16 + c16];
+    }
 
     // ---- activations next (they must not queue behind the weight ring), then fill the ring ----
-    UnitInfo cur = lsk_unit_info<NW>(0, units, ntl, ksteps, tile0, w, lane);
+    UnitInfo cur = lsk_unit_info<NW, lsk_wfmt<WF>::WB>(0, units, ntl, ksteps, tile0, w, lane);
     LSK_TRACE_POINT(9);                                           // address arithmetic done, nothing requested yet
     elem8 xr[MB];
     elem8 nw = {};
     float ss[MB];
     float sv[MB];                 // per-row 1/rms (PRO_RMS), wave-uniform
-    u32x4 ring[LSK_SPW * LSK_LPF];      // fp32: two 16-byte halves per fragment (lsk_ring_fill)
+    typename lsk_wfmt<WF>::slot_t ring[lsk_wfmt<WF>::SLOTS];      // fp32: two 16-byte halves per fragment (lsk_ring_fill); FP8 weights: 8-byte slots
     // Multi-row RMSNorm launches of a one-chunk K (the verify pass's q/k/v, gate/up and lm_head at hidden <= 4096): the normalisation
     // of 8 rows is ~450 VALU instructions per thread, ~2 us for the CU whoever executes them, and it used to start only when the LAST
     // wave was through the throttled issue of its ring (4.4 us: requests leave a CU at the HBM rate) -- a hole in the stream, rows staged
@@ -302,7 +354,7 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
                 for (int i = 0; i < MB; ++i) xr2[i] = *(const elem8*)(hp.x + (size_t)min(i, M - 1) * hp.ldx + k1);
             }
 #pragma unroll
-            for (int s = 0; s < LSK_SPW; ++s) lsk_ring_fill(ring, s, rsrc, cur, s < cur.nvalid);
+            for (int s = 0; s < LSK_SPW; ++s) lsk_ring_fill_wf(WF, ring, s, rsrc, cur, s < cur.nvalid);
             lsk_accumulate_squares<MB>(xr, tid * 8 < cur.steps_c * 32, ss);
             lsk_accumulate_squares<MB>(xr2, (tid + THREADS / 2) * 8 < cur.steps_c * 32, ss2);
 #pragma unroll
@@ -328,7 +380,7 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
             lsk_store_chunk<PRO, MB>(hp, xs, xstride, sv, cur.steps_c, tid + THREADS / 2, xr2, nw2);
         } else {
 #pragma unroll
-            for (int s = 0; s < LSK_SPW; ++s) lsk_ring_fill(ring, s, rsrc, cur, s < cur.nvalid);
+            for (int s = 0; s < LSK_SPW; ++s) lsk_ring_fill_wf(WF, ring, s, rsrc, cur, s < cur.nvalid);
         }
         LSK_TRACE_POINT(1);
     } else {
@@ -349,7 +401,7 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
         lsk_load_chunk<PRO, MB, NW>(hp, 0, cur.steps_c, tid, xr, nw);
     }
 #pragma unroll
-    for (int s = 0; s < LSK_SPW; ++s) lsk_ring_fill(ring, s, rsrc, cur, s < cur.nvalid);
+    for (int s = 0; s < LSK_SPW; ++s) lsk_ring_fill_wf(WF, ring, s, rsrc, cur, s < cur.nvalid);
     LSK_TRACE_POINT(1);                                           // rows and weight ring requested
     if (PRO == PRO_RMS) {
         lsk_accumulate_squares<MB>(xr, tid * 8 < cur.steps_c * 32, ss);
@@ -419,7 +471,7 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
     for (int s = 0; s < LSK_SPW; ++s) afr[s] = *(const elem8*)(xa + min(cur.ks0 + s, cur.steps_c - 1) * (32 * LSK_EB));
 
     for (int u = 0; u < units; ++u) {
-        const UnitInfo nxt = lsk_unit_info<NW>(u + 1, units, ntl, ksteps, tile0, w, lane);
+        const UnitInfo nxt = lsk_unit_info<NW, lsk_wfmt<WF>::WB>(u + 1, units, ntl, ksteps, tile0, w, lane);
         if (nchunks > 1 && cur.tl == 0 && u > 0) {
             // every wave passed the previous unit's barrier => nobody still reads the old chunk; the rows
             // of this chunk were prefetched into xr one chunk ago, the next chunk's are requested now
@@ -430,6 +482,9 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
 #pragma unroll
             for (int s = 0; s < LSK_SPW; ++s) afr[s] = *(const elem8*)(xa + min(cur.ks0 + s, cur.steps_c - 1) * (32 * LSK_EB));
         }
+        [[maybe_unused]] float scn;
+        if constexpr (WF == LSK_WF_FP8 && EPI == EPI_HEAD)      // (an exhausted `nxt` names tile 0 of the workgroup: valid, unused)
+            scn = ((const float*)((const unsigned char*)hp.wp + hp.wp_bytes))[(tile0 + nxt.tl) * 16 + c16];
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < LSK_SPW; ++s) {
@@ -438,7 +493,7 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
             if (u == 0 && s == 0) LSK_TRACE_POINT(3);             // first weight fragment arrived
             if (u == 0 && s == LSK_SPW - 1) LSK_TRACE_POINT(4);   // first unit's fragments all arrived
 #endif
-            lsk_ring_fill(ring, s, rsrc, nxt, s < nxt.nvalid);
+            lsk_ring_fill_wf(WF, ring, s, rsrc, nxt, s < nxt.nvalid);
             // (hipcc sinks these refills into bursts behind later MFMAs, so the ring runs ~8-16 deep; pinning
             //  "consume s -> refill s" with sched_barrier(0) gives the textbook vmcnt(15) stream but measured
             //  0..-4 % on every shape -- the HBM pipe is already full at ~8 KiB per wave in flight)
@@ -452,13 +507,21 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
             f32x4 t = *(const f32x4*)sb;
 #pragma unroll
             for (int ww = 1; ww < WAVES; ++ww) t += *(const f32x4*)(sb + ww * 256);
-            if (EPI == EPI_HEAD && nchunks == 1) lsk_head_tile(p, t, (tile0 + cur.tl) * 16 + c16, hp.N, M, rg, rbv, rbi);
-            else if (EPI == EPI_SWIGLU && (cur.tl & 1)) own1 += t;
+            if (EPI == EPI_HEAD && nchunks == 1) {
+                if constexpr (WF == LSK_WF_FP8) t *= scu;
+                lsk_head_tile(p, t, (tile0 + cur.tl) * 16 + c16, hp.N, M, rg, rbv, rbi);
+            } else if (EPI == EPI_SWIGLU && (cur.tl & 1)) own1 += t;
             else own0 += t;
         }
+        if constexpr (WF == LSK_WF_FP8 && EPI == EPI_HEAD) scu = scn;
         cur = nxt;
     }
     LSK_TRACE_POINT(5);                                           // last unit reduced
+    // FP8 weights: the rows' powers of two, once, on the reduced fp32 sums and in front of every rounding below
+    if constexpr (WF == LSK_WF_FP8) {
+        own0 *= sc0;
+        if (EPI == EPI_SWIGLU) own1 *= sc1;
+    }
 
     // ---- epilogue: owner wave `ow` holds tile (tile0 + ow) [pair ow for SWIGLU] in C layout ----
 
@@ -569,7 +632,7 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
 #endif
 }
 
-template <int PRO, int EPI, int MB, int NW>
+template <int PRO, int EPI, int MB, int NW, int WF = LSK_WF_ELEM>
 __global__ __launch_bounds__(NW * 64) void lsk_gemm_kernel(const elem_t* x, const elem_t* wp, const void* a2, const void* a3, int ldx, int K,
                                                                unsigned wp_bytes, int N, int m_tpw, unsigned e0, const GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -581,7 +644,7 @@ __global__ __launch_bounds__(NW * 64) void lsk_gemm_kernel(const elem_t* x, cons
     hp.h = (EPI == EPI_RESID) ? (elem_t*)const_cast<void*>(a2) : nullptr;
     hp.ldh = (EPI == EPI_RESID) ? (int)e0 : 0;
     hp.kv_len = (EPI == EPI_QKV) ? (const int*)a3 : nullptr;
-    lsk_gemm_body<PRO, EPI, MB, NW>(hp, p, blockIdx.x, smem);
+    lsk_gemm_body<PRO, EPI, MB, NW, WF>(hp, p, blockIdx.x, smem);
 }
 
 // the explicit-argument list of a launch, from the block (host side)

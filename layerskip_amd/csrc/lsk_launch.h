@@ -32,22 +32,35 @@ static const size_t kMaxGemmLds = 160 * 1024;
 #define LSK_MB_9 10
 #define LSK_MB_11 13
 
-template <int PRO, int EPI, int NW>
+// The FP8 weight format (lsk_gemm.h) exists in the bf16 build, for the projections of the engine (the fp32-output form is the kernel
+// tests' alone and has no FP8 instance).
+template <int EPI>
+constexpr bool lsk_has_fp8() { return LSK_ELEM_DTYPE == 0 && EPI != EPI_F32; }
+// ... and in eight waves only where lsk_gemm_waves can choose eight: the RMSNorm launches other than the lm_head (the bf16 format's
+// eight-wave forms of the others exist for -DLSK_FORCE_WAVES=8 measurement builds)
+template <int PRO, int EPI>
+constexpr bool lsk_has_fp8_8w() { return lsk_has_fp8<EPI>() && PRO == PRO_RMS && EPI != EPI_HEAD; }
+
+template <int PRO, int EPI, int NW, int WF>
 static int set_gemm_attr_nw() {
-    HIP_OK(hipFuncSetAttribute((const void*)lsk_gemm_kernel<PRO, EPI, 1, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxGemmLds));
-    HIP_OK(hipFuncSetAttribute((const void*)lsk_gemm_kernel<PRO, EPI, LSK_MB_MID, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxGemmLds));
-    HIP_OK(hipFuncSetAttribute((const void*)lsk_gemm_kernel<PRO, EPI, LSK_MB_9, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxGemmLds));
-    HIP_OK(hipFuncSetAttribute((const void*)lsk_gemm_kernel<PRO, EPI, LSK_MB_11, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxGemmLds));
-    HIP_OK(hipFuncSetAttribute((const void*)lsk_gemm_kernel<PRO, EPI, 16, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxGemmLds));
+    HIP_OK(hipFuncSetAttribute((const void*)lsk_gemm_kernel<PRO, EPI, 1, NW, WF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxGemmLds));
+    HIP_OK(hipFuncSetAttribute((const void*)lsk_gemm_kernel<PRO, EPI, LSK_MB_MID, NW, WF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxGemmLds));
+    HIP_OK(hipFuncSetAttribute((const void*)lsk_gemm_kernel<PRO, EPI, LSK_MB_9, NW, WF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxGemmLds));
+    HIP_OK(hipFuncSetAttribute((const void*)lsk_gemm_kernel<PRO, EPI, LSK_MB_11, NW, WF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxGemmLds));
+    HIP_OK(hipFuncSetAttribute((const void*)lsk_gemm_kernel<PRO, EPI, 16, NW, WF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxGemmLds));
     return 0;
 }
 
 template <int PRO, int EPI>
 static int set_gemm_attr() {
-    LSK_TRY((set_gemm_attr_nw<PRO, EPI, 4>()));
+    LSK_TRY((set_gemm_attr_nw<PRO, EPI, 4, LSK_WF_ELEM>()));
 #if LSK_EB == 2
-    LSK_TRY((set_gemm_attr_nw<PRO, EPI, 8>()));
+    LSK_TRY((set_gemm_attr_nw<PRO, EPI, 8, LSK_WF_ELEM>()));
 #endif
+    if constexpr (lsk_has_fp8<EPI>()) {
+        LSK_TRY((set_gemm_attr_nw<PRO, EPI, 4, LSK_WF_FP8>()));
+        if constexpr (lsk_has_fp8_8w<PRO, EPI>()) LSK_TRY((set_gemm_attr_nw<PRO, EPI, 8, LSK_WF_FP8>()));
+    }
     return 0;
 }
 
@@ -92,17 +105,17 @@ static int tiles_per_wg(int n_units, int target_wgs, int max_units) {   // units
     return t < 1 ? 1 : (t > max_units ? max_units : t);
 }
 
-template <int PRO, int EPI, int MB, int NW>
+template <int PRO, int EPI, int MB, int NW, int WF>
 static void launch_gemm_mb(const GemmParams& p, int grid, size_t lds, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
     // the fields a workgroup needs before its first weight request ride in front of the block (GemmHot, lsk_gemm.h)
     const GemmHotArgs<PRO, EPI> a(p);
-    if (ev_start != nullptr) hipExtLaunchKernelGGL((lsk_gemm_kernel<PRO, EPI, MB, NW>), dim3(grid), dim3(NW * 64), lds, st, ev_start, ev_stop, 0,
+    if (ev_start != nullptr) hipExtLaunchKernelGGL((lsk_gemm_kernel<PRO, EPI, MB, NW, WF>), dim3(grid), dim3(NW * 64), lds, st, ev_start, ev_stop, 0,
                                                    p.x, p.wp, a.a2, a.a3, p.ldx, p.K, p.wp_bytes, p.N, a.m_tpw, a.e0, p);
-    else hipLaunchKernelGGL((lsk_gemm_kernel<PRO, EPI, MB, NW>), dim3(grid), dim3(NW * 64), lds, st,
+    else hipLaunchKernelGGL((lsk_gemm_kernel<PRO, EPI, MB, NW, WF>), dim3(grid), dim3(NW * 64), lds, st,
                             p.x, p.wp, a.a2, a.a3, p.ldx, p.K, p.wp_bytes, p.N, a.m_tpw, a.e0, p);
 }
 
-template <int PRO, int EPI, int NW>
+template <int PRO, int EPI, int NW, int WF>
 static int launch_gemm_nw(GemmParams& p, int target_wgs, hipStream_t st, int* grid_out, hipEvent_t ev_start, hipEvent_t ev_stop) {
     const int unit = (EPI == EPI_SWIGLU) ? 2 : 1;
     const int n_units = p.n_tiles / unit;
@@ -115,16 +128,16 @@ static int launch_gemm_nw(GemmParams& p, int target_wgs, hipStream_t st, int* gr
     if (p.n_tiles != (p.N + 15) / 16) return lsk_fail("gemm: n_tiles %d is not ceil(N / 16) of N = %d", p.n_tiles, p.N);   // the kernel derives it
     if (lds > kMaxGemmLds) return lsk_fail("gemm LDS %zu exceeds %zu", lds, kMaxGemmLds);
     // 32-bit buffer offsets; the out-of-range sentinel of ragged ring slots must stay beyond the descriptor's range
-    if ((size_t)p.n_tiles * 16 * (size_t)p.K * sizeof(elem_t) >= (size_t)LSK_OOB_OFFSET) return lsk_fail("packed weight of %d x %d exceeds the 32-bit buffer range", p.n_tiles * 16, p.K);
+    if ((size_t)p.n_tiles * 16 * (size_t)p.K * (size_t)lsk_wfmt<WF>::WB >= (size_t)LSK_OOB_OFFSET) return lsk_fail("packed weight of %d x %d exceeds the 32-bit buffer range", p.n_tiles * 16, p.K);
 #ifdef LSK_TRACE
     p.trace = lsk_trace_next(0, (PRO * 16 + EPI) | (p.K << 8), p.M, grid);
 #endif
     // profiling (ev_start != nullptr): the events are bound to THIS dispatch's own begin / end timestamps (what rocprofv3 reports)
-    if (p.M == 1) launch_gemm_mb<PRO, EPI, 1, NW>(p, grid, lds, st, ev_start, ev_stop);
-    else if (p.M <= LSK_MB_MID) launch_gemm_mb<PRO, EPI, LSK_MB_MID, NW>(p, grid, lds, st, ev_start, ev_stop);
-    else if (p.M <= LSK_MB_9) launch_gemm_mb<PRO, EPI, LSK_MB_9, NW>(p, grid, lds, st, ev_start, ev_stop);
-    else if (p.M <= LSK_MB_11) launch_gemm_mb<PRO, EPI, LSK_MB_11, NW>(p, grid, lds, st, ev_start, ev_stop);
-    else launch_gemm_mb<PRO, EPI, 16, NW>(p, grid, lds, st, ev_start, ev_stop);
+    if (p.M == 1) launch_gemm_mb<PRO, EPI, 1, NW, WF>(p, grid, lds, st, ev_start, ev_stop);
+    else if (p.M <= LSK_MB_MID) launch_gemm_mb<PRO, EPI, LSK_MB_MID, NW, WF>(p, grid, lds, st, ev_start, ev_stop);
+    else if (p.M <= LSK_MB_9) launch_gemm_mb<PRO, EPI, LSK_MB_9, NW, WF>(p, grid, lds, st, ev_start, ev_stop);
+    else if (p.M <= LSK_MB_11) launch_gemm_mb<PRO, EPI, LSK_MB_11, NW, WF>(p, grid, lds, st, ev_start, ev_stop);
+    else launch_gemm_mb<PRO, EPI, 16, NW, WF>(p, grid, lds, st, ev_start, ev_stop);
     HIP_OK(hipGetLastError());
     if (grid_out) *grid_out = grid;
     return 0;
@@ -134,11 +147,22 @@ static int launch_gemm_nw(GemmParams& p, int target_wgs, hipStream_t st, int* gr
 template <int PRO, int EPI>
 static int launch_gemm(GemmParams& p, int target_wgs, hipStream_t st, int* grid_out = nullptr, hipEvent_t ev_start = nullptr,
                        hipEvent_t ev_stop = nullptr) {
+    if (p.wfmt != LSK_WF_ELEM) {
+        // the same lsk_gemm_waves rule as the bf16 format: the summation order of an output element is the bf16 kernel's
+        if constexpr (lsk_has_fp8<EPI>()) {
+            if (p.wfmt != LSK_WF_FP8) return lsk_fail("gemm: unknown weight format %d", p.wfmt);
+            if (lsk_gemm_waves(PRO, EPI, p.K) == 4) return launch_gemm_nw<PRO, EPI, 4, LSK_WF_FP8>(p, target_wgs, st, grid_out, ev_start, ev_stop);
+            if constexpr (lsk_has_fp8_8w<PRO, EPI>()) return launch_gemm_nw<PRO, EPI, 8, LSK_WF_FP8>(p, target_wgs, st, grid_out, ev_start, ev_stop);
+            else return lsk_fail("gemm: no eight-wave FP8 form of this projection (LSK_FORCE_WAVES measurement builds: bf16 format only)");
+        } else {
+            return lsk_fail("gemm: this build / projection has no kernel for weight format %d", p.wfmt);
+        }
+    }
 #if LSK_EB == 4
-    return launch_gemm_nw<PRO, EPI, 4>(p, target_wgs, st, grid_out, ev_start, ev_stop);   // (lsk_gemm_waves: the eight-wave forms are not built)
+    return launch_gemm_nw<PRO, EPI, 4, LSK_WF_ELEM>(p, target_wgs, st, grid_out, ev_start, ev_stop);   // (lsk_gemm_waves: the eight-wave forms are not built)
 #else
-    if (lsk_gemm_waves(PRO, EPI, p.K) == 4) return launch_gemm_nw<PRO, EPI, 4>(p, target_wgs, st, grid_out, ev_start, ev_stop);
-    return launch_gemm_nw<PRO, EPI, 8>(p, target_wgs, st, grid_out, ev_start, ev_stop);
+    if (lsk_gemm_waves(PRO, EPI, p.K) == 4) return launch_gemm_nw<PRO, EPI, 4, LSK_WF_ELEM>(p, target_wgs, st, grid_out, ev_start, ev_stop);
+    return launch_gemm_nw<PRO, EPI, 8, LSK_WF_ELEM>(p, target_wgs, st, grid_out, ev_start, ev_stop);
 #endif
 }
 
@@ -154,19 +178,21 @@ struct GemmLaunch {
 };
 
 // m rows of x ([m][K]) against the packed weight of N output features
-static GemmParams gemm_params(const elem_t* x, int m, int K, const elem_t* wp, int N) {
+// (wfmt: the format of wp -- LSK_WF_ELEM, or LSK_WF_FP8: 1-byte codes, wp_bytes counts them)
+static GemmParams gemm_params(const elem_t* x, int m, int K, const elem_t* wp, int N, int wfmt = LSK_WF_ELEM) {
     GemmParams p{};
     p.x = x; p.ldx = K; p.M = m; p.K = K; p.N = N; p.n_tiles = (N + 15) / 16;
-    p.wp = wp; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * K * sizeof(elem_t));
+    p.wp = wp; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * K * (wfmt == LSK_WF_FP8 ? 1 : sizeof(elem_t)));
+    p.wfmt = wfmt;
     return p;
 }
 
 // input RMSNorm -> q/k/v projections -> RoPE -> KV append: row i sits at position *kv_len + pos_off + i; q -> q_out, k / v -> the pages
 static GemmLaunch<PRO_RMS, EPI_QKV> gemm_qkv(const lsk_config& c, const elem_t* x, int m, const elem_t* wqkv, const elem_t* norm_w,
                                              const elem_t* rope_cos, const elem_t* rope_sin, const int* kv_len, int pos_off,
-                                             const int* block_table, elem_t* q_out, elem_t* kpool, elem_t* vpool) {
+                                             const int* block_table, elem_t* q_out, elem_t* kpool, elem_t* vpool, int wfmt = LSK_WF_ELEM) {
     const int qdim = c.n_heads * c.head_dim;
-    GemmLaunch<PRO_RMS, EPI_QKV> g{gemm_params(x, m, c.hidden, wqkv, qdim + 2 * c.n_kv_heads * c.head_dim)};
+    GemmLaunch<PRO_RMS, EPI_QKV> g{gemm_params(x, m, c.hidden, wqkv, qdim + 2 * c.n_kv_heads * c.head_dim, wfmt)};
     GemmParams& p = g.p;
     p.norm_w = norm_w; p.eps = c.rms_eps;
     p.q_out = q_out; p.ldq = qdim; p.kpool = kpool; p.vpool = vpool; p.block_table = block_table;
@@ -176,24 +202,24 @@ static GemmLaunch<PRO_RMS, EPI_QKV> gemm_qkv(const lsk_config& c, const elem_t* 
 }
 
 // o_proj / down_proj: x ([m][K]) against N features, added in place to the residual rows h ([m][N])
-static GemmLaunch<PRO_PLAIN, EPI_RESID> gemm_resid(const elem_t* x, int m, int K, const elem_t* wp, int N, elem_t* h) {
-    GemmLaunch<PRO_PLAIN, EPI_RESID> g{gemm_params(x, m, K, wp, N)};
+static GemmLaunch<PRO_PLAIN, EPI_RESID> gemm_resid(const elem_t* x, int m, int K, const elem_t* wp, int N, elem_t* h, int wfmt = LSK_WF_ELEM) {
+    GemmLaunch<PRO_PLAIN, EPI_RESID> g{gemm_params(x, m, K, wp, N, wfmt)};
     g.p.h = h; g.p.ldh = N;
     return g;
 }
 
 // post-attention RMSNorm -> gate/up projections -> SiLU(gate) * up -> act ([m][intermediate])
 static GemmLaunch<PRO_RMS, EPI_SWIGLU> gemm_swiglu(const lsk_config& c, const elem_t* x, int m, const elem_t* wgu, const elem_t* norm_w,
-                                                   elem_t* act) {
-    GemmLaunch<PRO_RMS, EPI_SWIGLU> g{gemm_params(x, m, c.hidden, wgu, 2 * c.intermediate)};
+                                                   elem_t* act, int wfmt = LSK_WF_ELEM) {
+    GemmLaunch<PRO_RMS, EPI_SWIGLU> g{gemm_params(x, m, c.hidden, wgu, 2 * c.intermediate, wfmt)};
     g.p.norm_w = norm_w; g.p.eps = c.rms_eps; g.p.act = act; g.p.ldact = c.intermediate;
     return g;
 }
 
 // final RMSNorm -> lm_head: fp32 logits rows (logits != nullptr) and per-workgroup argmax candidates in part_val / part_idx
 static GemmLaunch<PRO_RMS, EPI_HEAD> gemm_head(const lsk_config& c, const elem_t* x, int m, const elem_t* lm_head, const elem_t* norm_w,
-                                               float* logits, int ld_logits, float* part_val, int* part_idx) {
-    GemmLaunch<PRO_RMS, EPI_HEAD> g{gemm_params(x, m, c.hidden, lm_head, c.vocab)};
+                                               float* logits, int ld_logits, float* part_val, int* part_idx, int wfmt = LSK_WF_ELEM) {
+    GemmLaunch<PRO_RMS, EPI_HEAD> g{gemm_params(x, m, c.hidden, lm_head, c.vocab, wfmt)};
     GemmParams& p = g.p;
     p.norm_w = norm_w; p.eps = c.rms_eps;
     p.logits = logits; p.ld_logits = ld_logits; p.part_val = part_val; p.part_idx = part_idx;

@@ -32,6 +32,89 @@ __global__ void lsk_pack_kernel(const elem_t* __restrict__ src, int n_rows, int 
     *(elem8*)(dst + ((dt * ksteps + s) * 64 + lane) * 8) = v;
 }
 
+// ---- FP8 (OCP e4m3fn) weight storage: the device quantiser.  The format's specification is layerskip_amd/quant.py, which this agrees
+// with bit for bit: per output row one power of two 2^k, k the smallest exponent with amax_row <= 448 * 2^k (k = 0 for an all-zero row,
+// k >= -117 so that the smallest code times 2^k is a bf16 normal), codes = e4m3(w / 2^k) rounded to nearest even.
+// Everything is integer / exact fp32 arithmetic, so host and device cannot disagree by a rounding mode.
+__host__ __device__ inline int lsk_fp8_row_exponent(float amax) {
+    const unsigned b = __builtin_bit_cast(unsigned, amax);
+    const int E = (int)((b >> 23) & 0xffu);
+    if (b == 0u) return 0;
+    if (E == 0) return -117;                                   // fp32 (= bf16) subnormal amax: far below the clamp
+    // amax = 1.f x 2^(E - 127); 448 = 1.75 x 2^8: k = E - 127 - 8, one more when 1.f > 1.75
+    const int k = E - 135 + ((b & 0x7fffffu) > 0x600000u ? 1 : 0);
+    return k < -117 ? -117 : k;
+}
+__host__ __device__ inline float lsk_pow2f(int k) { return __builtin_bit_cast(float, (unsigned)(127 + k) << 23); }   // -126 <= k <= 127
+// |x| <= 448 -> the e4m3fn code of x rounded to nearest even (subnormal codes below 2^-6, -0 and tiny negatives keep their sign)
+__host__ __device__ inline unsigned lsk_e4m3_encode(float x) {
+    const unsigned b = __builtin_bit_cast(unsigned, x);
+    const unsigned sign = (b >> 24) & 0x80u;
+    const float a = __builtin_bit_cast(float, b & 0x7fffffffu);
+    int E = (int)((b >> 23) & 0xffu) - 127;
+    if (E < -6) E = -6;
+    int r = (int)rintf(a * lsk_pow2f(3 - E));                  // a in units of 2^(E - 3): 8 .. 16 (0 .. 8 in the subnormal range), exact scaling
+    if (r == 16) { r = 8; E += 1; }
+    return sign | (r < 8 ? (unsigned)r : (unsigned)(((E + 7) << 3) | (r - 8)));
+}
+
+// bf16 nn.Linear weight -> e4m3 codes in lsk_pack_kernel's tile order (1-byte elements: a lane's fragment is 8 B) + the fp32 power of
+// two of every PACKED row at dst + dst_rows * k + 4 * packed row (dst_rows: rows of the whole destination buffer, a multiple of 16).
+// One workgroup per packed row: row amax, then one lane-fragment per thread and pass.  Rows beyond n_rows (the padding of a ragged
+// last tile): code 0, scale 1.
+#if LSK_ELEM_DTYPE == 0
+__global__ __launch_bounds__(256) void lsk_pack_fp8_kernel(const elem_t* __restrict__ src, int n_rows, int k, int ld_src,
+                                                           unsigned char* __restrict__ dst, int dst_rows, int dst_tile_offset,
+                                                           int dst_tile_stride, int rope_hd) {
+    __shared__ float part[4];
+    const int ksteps = k >> 5;
+    const int rp = blockIdx.x;                    // row in packed order (of this source)
+    const int t = rp >> 4;
+    int srow = rp;
+    if (rope_hd > 0) {
+        const int head = rp / rope_hd;
+        const int r = rp - head * rope_hd;
+        const int tt = r >> 4;
+        const int cc = r & 15;
+        const int feat = (cc < 8) ? (tt * 8 + cc) : ((rope_hd >> 1) + tt * 8 + (cc - 8));
+        srow = head * rope_hd + feat;
+    }
+    const bool live = srow < n_rows;
+    const elem_t* row = src + (size_t)(live ? srow : 0) * ld_src;
+    float amax = 0.f;
+    if (live)
+        for (int f = threadIdx.x; f < (k >> 3); f += blockDim.x) {
+            const elem8 v = *(const elem8*)(row + f * 8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf((float)v[j]));
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = amax;
+    __syncthreads();
+    amax = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
+    const int kexp = lsk_fp8_row_exponent(amax);
+    const float inv = lsk_pow2f(-kexp);
+    const size_t dt = (size_t)dst_tile_offset + (size_t)t * dst_tile_stride;
+    for (int f = threadIdx.x; f < (k >> 3); f += blockDim.x) {
+        unsigned lo = 0u, hi = 0u;
+        if (live) {
+            const elem8 v = *(const elem8*)(row + f * 8);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                lo |= lsk_e4m3_encode((float)v[j] * inv) << (8 * j);
+                hi |= lsk_e4m3_encode((float)v[4 + j] * inv) << (8 * j);
+            }
+        }
+        const int s = f >> 2;                                  // k-step
+        const int lane = ((f & 3) << 4) | (rp & 15);
+        uint2 out; out.x = lo; out.y = hi;
+        *(uint2*)(dst + ((dt * ksteps + s) * 64 + lane) * 8) = out;
+    }
+    if (threadIdx.x == 0) ((float*)(dst + (size_t)dst_rows * k))[dt * 16 + (rp & 15)] = live ? lsk_pow2f(kexp) : 1.0f;
+}
+#endif
+
 // h[row_base + i] = embed[tokens[i]]   (tokens on device)
 __global__ void lsk_embed_kernel(const elem_t* __restrict__ embed, const int* __restrict__ tokens, int hidden, int vocab,
                                  elem_t* __restrict__ h) {

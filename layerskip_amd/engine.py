@@ -76,8 +76,11 @@ class HipEngine:
         return eos, _i32_array(eos)
 
     def __init__(self, model, max_ctx: int = 2048, max_prompt: int = 1024, page_size: int = 128,
-                 target_wgs: int = 0, layer_range: Optional[Sequence[int]] = None, release_weights: bool = False):
+                 target_wgs: int = 0, layer_range: Optional[Sequence[int]] = None, release_weights: bool = False,
+                 weight_format: str = "bf16"):
         cfg = model.config
+        if weight_format not in _lib.WEIGHT_FORMATS:
+            raise _lib.LskError(f"unknown weight_format {weight_format!r} ({' | '.join(_lib.WEIGHT_FORMATS)})")
         # (the final norm is the one tensor every rank of a pipeline materialises: a middle rank holds neither the embedding nor the head)
         weight = model.model.norm.weight if model.model.embed_tokens.weight.is_meta else model.model.embed_tokens.weight
         dmap = getattr(model, "hf_device_map", None)
@@ -98,6 +101,17 @@ class HipEngine:
             self.dtype, dtype_name = torch.float32, "fp32"
         else:
             raise _lib.LskError(f"HipEngine computes in bf16, fp16 or fp32; model dtype is {weight.dtype}")
+        # weight_format="fp8_e4m3" (opt-in; "bf16" = the model dtype, the default): the projections are stored as e4m3 codes with one
+        # power of two per output row (layerskip_amd/quant.py) and the decode path streams half the bytes; bit-identical to this engine
+        # in bf16 on quant.dequantized_model(model).  The bf16 library only.
+        if weight_format != "bf16" and dtype_name != "bf16":
+            raise _lib.LskError(f"weight_format={weight_format!r} needs a bf16 model; this one is {dtype_name} "
+                                "(FP8 weight storage exists in the bf16 build only)")
+        self.weight_format = weight_format
+        # what the MFMA-tiled prefill kernels read under FP8: bf16-packed copies of the DEQUANTISED projections (same values as the codes,
+        # so prompt KV and exit hiddens are the bf16 engine's on the dequantised model; packed bytes are 1.5 x bf16's instead of 0.5 x,
+        # DESIGN.md 3.1).  None in the default format: one set of buffers serves both paths.
+        self.prefill_weights = "bf16_copy_of_dequantized" if weight_format == "fp8_e4m3" else None
         self.lib = _lib.load(dtype=dtype_name)
         self.elem_bytes = torch.empty(0, dtype=self.dtype).element_size()
         # sample=True on the device: the sampler's 16-bit logit keys are exact at bf16 / fp16 only (lsk_key16, lsk_sample.h).  Over fp32
@@ -131,6 +145,7 @@ class HipEngine:
         self.release_weights = release_weights
         self._handle = ctypes.c_void_p(None)
         self._packed = []           # per-layer packed buffers (kept alive); None outside layer_range
+        self._packed_prefill = []   # FP8 format: per-layer (wqkv, wo, wgu, wdown) bf16-packed dequantised copies for the prefill kernels
         self._globals = {}
         self._buffers = {}
         self._options = {}          # lsk_engine_set_option values, re-applied whenever the C engine is recreated
@@ -195,6 +210,7 @@ class HipEngine:
             raise _lib.LskError("refresh_weights: this engine released the original weights (release_weights=True)")
         with torch.cuda.device(self.device):
             self._packed = []
+            self._packed_prefill = []
             self._globals = {}
             self._pack_weights(model)
             self._bind_weights()
@@ -205,19 +221,57 @@ class HipEngine:
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def _packed_buffer(self, n_rows: int, k: int) -> torch.Tensor:
-        nbytes = ctypes.c_size_t(0)
-        self._ck(self.lib.lsk_packed_bytes(n_rows, k, ctypes.byref(nbytes)))
-        return torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+    @property
+    def _fp8(self) -> bool:
+        return self.weight_format == "fp8_e4m3"
 
-    def _pack_into(self, dst: torch.Tensor, w: torch.Tensor, tile_offset: int, tile_stride: int, rope_hd: int) -> None:
+    def _packed_buffer(self, n_rows: int, k: int, prefill_copy: bool = False):
+        """The packed buffer of an [n_rows][k] projection in the engine's weight format.  FP8: a (buffer, rows, prefill) triple --
+        the FP8 buffer, its rows (which locate the scale table) and, with `prefill_copy`, the bf16-packed buffer of the dequantised
+        weights the prefill kernels read."""
+        nbytes = ctypes.c_size_t(0)
+        if not self._fp8:
+            self._ck(self.lib.lsk_packed_bytes(n_rows, k, ctypes.byref(nbytes)))
+            return torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        self._ck(self.lib.lsk_packed_bytes_fp8(n_rows, k, ctypes.byref(nbytes)))
+        buf = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        pf = None
+        if prefill_copy:
+            self._ck(self.lib.lsk_packed_bytes(n_rows, k, ctypes.byref(nbytes)))
+            pf = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        return (buf, _round_up(n_rows, 16), pf)
+
+    def _pack_into(self, dst, w: torch.Tensor, tile_offset: int, tile_stride: int, rope_hd: int) -> None:
         w = w.detach()
         if w.dtype != self.dtype or w.device != self.device:
             raise _lib.LskError(f"all projection weights must be {self.dtype} on the engine's device")
         if w.stride(1) != 1:
             w = w.contiguous()
-        self._ck(self.lib.lsk_pack_linear(w.data_ptr(), w.shape[0], w.shape[1], w.stride(0), dst.data_ptr(),
-                                       tile_offset, tile_stride, rope_hd, self._stream))
+        if not self._fp8:
+            self._ck(self.lib.lsk_pack_linear(w.data_ptr(), w.shape[0], w.shape[1], w.stride(0), dst.data_ptr(),
+                                           tile_offset, tile_stride, rope_hd, self._stream))
+            return
+        buf, rows, pf = dst
+        self._ck(self.lib.lsk_pack_linear_fp8(w.data_ptr(), w.shape[0], w.shape[1], w.stride(0), buf.data_ptr(), rows,
+                                           tile_offset, tile_stride, rope_hd, self._stream))
+        if pf is not None:
+            from . import quant
+            d = quant.dequantize_weight(w)           # (the format's specification, run on the device; the device quantiser agrees bit for bit)
+            self._ck(self.lib.lsk_pack_linear(d.data_ptr(), d.shape[0], d.shape[1], d.stride(0), pf.data_ptr(),
+                                           tile_offset, tile_stride, rope_hd, self._stream))
+            torch.cuda.current_stream(self.device).synchronize()     # `d` is a temporary: the pack kernel must be through with it
+
+    def unpacked_fp8(self, layer: int, name: str):
+        """(codes uint8 [rows][k], scale fp32 [rows]) of a packed FP8 buffer in PACKED row order (quant.unpack_tiles); name: wqkv | wo |
+        wgu | wdown | lm_head."""
+        if not self._fp8:
+            raise _lib.LskError("unpacked_fp8: this engine stores its weights in the model dtype")
+        from . import quant
+        hd, H, I = self.head_dim, self.hidden, self.intermediate
+        shapes = {"wqkv": ((self.n_heads + 2 * self.n_kv_heads) * hd, H), "wo": (H, self.n_heads * hd), "wgu": (2 * I, H),
+                  "wdown": (H, I), "lm_head": (self.vocab, H)}
+        buf = self._globals["lm_head"] if name == "lm_head" else self._packed[layer][("wqkv", "wo", "wgu", "wdown").index(name)]
+        return quant.unpack_tiles(buf, *shapes[name])
 
     def _pack_weights(self, m) -> None:
         hd, H, I = self.head_dim, self.hidden, self.intermediate
@@ -225,21 +279,26 @@ class HipEngine:
         for idx, layer in enumerate(m.model.layers):
             if not (self.layer_range[0] <= idx < self.layer_range[1]):
                 self._packed.append(None)       # another pipeline rank owns this layer
+                if self._fp8:
+                    self._packed_prefill.append(None)
                 continue
             a, mlp = layer.self_attn, layer.mlp
-            wqkv = self._packed_buffer(qdim + 2 * kvdim, H)
+            wqkv = self._packed_buffer(qdim + 2 * kvdim, H, prefill_copy=True)
             self._pack_into(wqkv, a.q_proj.weight, 0, 1, hd)
             self._pack_into(wqkv, a.k_proj.weight, qdim // 16, 1, hd)
             self._pack_into(wqkv, a.v_proj.weight, (qdim + kvdim) // 16, 1, 0)
-            wo = self._packed_buffer(H, qdim)
+            wo = self._packed_buffer(H, qdim, prefill_copy=True)
             self._pack_into(wo, a.o_proj.weight, 0, 1, 0)
-            wgu = self._packed_buffer(2 * I, H)
+            wgu = self._packed_buffer(2 * I, H, prefill_copy=True)
             self._pack_into(wgu, mlp.gate_proj.weight, 0, 2, 0)
             self._pack_into(wgu, mlp.up_proj.weight, 1, 2, 0)
-            wdown = self._packed_buffer(H, I)
+            wdown = self._packed_buffer(H, I, prefill_copy=True)
             self._pack_into(wdown, mlp.down_proj.weight, 0, 1, 0)
             n1 = layer.input_layernorm.weight.detach().contiguous()
             n2 = layer.post_attention_layernorm.weight.detach().contiguous()
+            if self._fp8:
+                self._packed_prefill.append(tuple(t[2] for t in (wqkv, wo, wgu, wdown)))
+                wqkv, wo, wgu, wdown = (t[0] for t in (wqkv, wo, wgu, wdown))
             self._packed.append((wqkv, wo, wgu, wdown, n1, n2))
             if self.release_weights:
                 torch.cuda.synchronize(self.device)
@@ -252,7 +311,7 @@ class HipEngine:
         if have_head:
             head = self._packed_buffer(self.vocab, H)
             self._pack_into(head, m.lm_head.weight, 0, 1, 0)
-            self._globals["lm_head"] = head
+            self._globals["lm_head"] = head[0] if self._fp8 else head      # (no prefill copy: the head is a decode-path launch)
             tied = have_embed and m.lm_head.weight.data_ptr() == m.model.embed_tokens.weight.data_ptr()
             if self.release_weights and not tied:
                 torch.cuda.synchronize(self.device)
@@ -308,12 +367,16 @@ class HipEngine:
 
     def _bind_weights(self) -> None:
         handle = self._handle
+        if self._fp8:           # (the default format makes no call the parent ABI did not make)
+            self._ck(self.lib.lsk_engine_set_weight_format(handle, _lib.WEIGHT_FORMATS[self.weight_format]))
         for i, packed in enumerate(self._packed):
             if packed is None:
                 continue
             wqkv, wo, wgu, wdown, n1, n2 = packed
             self._ck(self.lib.lsk_engine_set_layer(handle, i, wqkv.data_ptr(), wo.data_ptr(), wgu.data_ptr(),
                                                 wdown.data_ptr(), n1.data_ptr(), n2.data_ptr()))
+            if self._fp8:
+                self._ck(self.lib.lsk_engine_set_layer_prefill(handle, i, *[t.data_ptr() for t in self._packed_prefill[i]]))
         g = self._globals
         ptr = lambda t: t.data_ptr() if t is not None else None          # noqa: E731 -- NULL: not bound on this rank
         self._ck(self.lib.lsk_engine_set_globals(handle, ptr(g["embed"]), ptr(g["final_norm"]), ptr(g["lm_head"]),
@@ -660,12 +723,16 @@ class HipEngine:
         hd = self.head_dim
         qdim, kvdim = self.n_heads * hd, self.n_kv_heads * hd
         eb = self.elem_bytes
+        if self._fp8:           # 1-byte codes + one fp32 power of two per packed row (the lm_head's rows pad to a whole tile)
+            size = lambda n, k: _round_up(n, 16) * (k + 4)       # noqa: E731
+        else:
+            size = lambda n, k: eb * n * k                         # noqa: E731
         return {
-            "qkv": eb * (qdim + 2 * kvdim) * self.hidden,
-            "o": eb * self.hidden * qdim,
-            "gate_up": eb * 2 * self.intermediate * self.hidden,
-            "down": eb * self.hidden * self.intermediate,
-            "lm_head": eb * self.vocab * self.hidden,
+            "qkv": size(qdim + 2 * kvdim, self.hidden),
+            "o": size(self.hidden, qdim),
+            "gate_up": size(2 * self.intermediate, self.hidden),
+            "down": size(self.hidden, self.intermediate),
+            "lm_head": size(self.vocab, self.hidden),
         }
 
 
@@ -685,10 +752,15 @@ def get_engine(model, check_weights: bool = True, **kwargs) -> HipEngine:
     if _ENGINES is None:
         import weakref
         _ENGINES = weakref.WeakKeyDictionary()
-    eng = _ENGINES.get(model)
+    # one engine per (model, weight format): a request for one format is never served by an engine of the other
+    fmt = kwargs.get("weight_format") or "bf16"
+    per_model = _ENGINES.get(model)
+    if per_model is None:
+        per_model = _ENGINES[model] = {}
+    eng = per_model.get(fmt)
     if eng is None:
         eng = HipEngine(model, **kwargs)
-        _ENGINES[model] = eng
+        per_model[fmt] = eng
         return eng
     if check_weights and eng.weights_changed(model):
         eng.refresh_weights(model)
