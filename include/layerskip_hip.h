@@ -139,9 +139,13 @@ int lsk_engine_set_layer(lsk_engine* e, int32_t layer, const void* wqkv, const v
  * engine, set before the first lsk_engine_set_layer.  A setter and not a field of lsk_config: the struct is passed by value-layout
  * across three libraries and the kernel-test library, and every existing caller constructs it positionally; a call the default
  * path never makes cannot change it.  LSK_WEIGHT_FORMAT_FP8_E4M3: the decode-path kernels (lsk_run_layers, lsk_run_head, the fused
- * steps) read ONLY the FP8 buffers; the MFMA-tiled prefill kernels (lsk_run_bulk from LSK_OPT_BIG_THRESHOLD rows on) read model-dtype
- * packed copies of the DEQUANTISED projections bound with lsk_engine_set_layer_prefill (lsk_pack_linear of quant.dequantize_rows):
- * same values, so prompt KV and exit hiddens are those of the bf16 engine on the dequantised model; packed bytes are 1.5 x bf16's. */
+ * steps) and the MFMA-tiled prefill kernels (lsk_run_bulk from LSK_OPT_BIG_THRESHOLD rows on) read the SAME FP8 buffers: one set of
+ * projection buffers per engine, 0.5 x the model-dtype format's bytes; prompt KV and exit hiddens are bit for bit those of the bf16
+ * engine on the dequantised model.
+ * lsk_engine_set_layer_prefill is OPTIONAL: it binds model-dtype packed copies of a layer's DEQUANTISED projections
+ * (lsk_pack_linear of quant.dequantize_rows: same values, same results); a layer that has them prefills from them through the
+ * model-dtype kernel instances, a layer without prefills from the codes.  All four buffers, or four NULLs to unbind the layer.  It is
+ * the path FP8 engines took before the prefill kernel read the codes, kept as the in-process A/B lever of tools/fp8_prefill_ab.py. */
 #define LSK_WEIGHT_FORMAT_ELEM 0       /* model dtype (default) */
 #define LSK_WEIGHT_FORMAT_FP8_E4M3 1
 int lsk_engine_set_weight_format(lsk_engine* e, int32_t weight_format);

@@ -9,7 +9,8 @@
 
 struct LayerWeights {
     const elem_t *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wdown = nullptr, *norm1 = nullptr, *norm2 = nullptr;
-    // FP8 weight format: model-dtype packed copies of the DEQUANTISED projections, read by the prefill kernels alone (lsk_engine_set_layer_prefill)
+    // FP8 weight format, optional (lsk_engine_set_layer_prefill): model-dtype packed copies of the DEQUANTISED projections.  A layer that has
+    // them prefills from them with the model-dtype kernels; a layer without (the default) prefills from the codes above
     const elem_t *pf_wqkv = nullptr, *pf_wo = nullptr, *pf_wgu = nullptr, *pf_wdown = nullptr;
 };
 

@@ -18,6 +18,7 @@
 // different accumulation order never reaches an argmax; it only fills KV pages / exit hiddens.
 #pragma once
 #include "lsk_common.h"
+#include "lsk_gemm.h"      // the weight formats (LSK_WF_*) and the e4m3 -> bf16 conversion of the decode kernel
 
 #define LSK_BIG_BK 64
 #define LSK_BIG_LDA (64 * LSK_EB + 32)   // bytes per LDS row: 64 elements + 32 B pad (bf16: slot (10r + g) mod 16, conflict-free A-fragment reads)
@@ -27,7 +28,7 @@ struct BigGemmParams {
     int ldx;
     int M;
     int K;                  // multiple of 64
-    const elem_t* wp;       // packed tiles
+    const elem_t* wp;       // packed tiles (LSK_WF_FP8: the 1-byte codes; the rows' fp32 powers of two follow them at byte 16 n_tiles K)
     int N;
     int n_tiles;
     // EPI_RESID
@@ -50,7 +51,22 @@ struct BigGemmParams {
     const elem_t* rope_sin;
     const int* kv_len;
     int pos_off;
+    int wfmt;               // host side only: format of wp (LSK_WF_ELEM | LSK_WF_FP8, lsk_gemm.h) -- picks the kernel instance
 };
+
+// A slot of the weight ring: a lane's fragment of one k-step of one packed tile -- 8 elements, or 8 e4m3 codes (8 bytes) that become 8 bf16
+// at consumption (lsk_fp8x2_to_bf16x2: exact)
+template <int WF> struct lsk_big_slot { typedef elem8 type; };
+#if LSK_ELEM_DTYPE == 0
+template <> struct lsk_big_slot<LSK_WF_FP8> { typedef u32x2 type; };
+__device__ __forceinline__ elem8 lsk_big_frag(const u32x2 c) {
+    u32x4 o;
+    o[0] = lsk_fp8x2_to_bf16x2(c[0], false); o[1] = lsk_fp8x2_to_bf16x2(c[0], true);
+    o[2] = lsk_fp8x2_to_bf16x2(c[1], false); o[3] = lsk_fp8x2_to_bf16x2(c[1], true);
+    return __builtin_bit_cast(elem8, o);
+}
+#endif
+__device__ __forceinline__ elem8 lsk_big_frag(const elem8 f) { return f; }
 
 // NTW = packed 16-column tiles per wave: 2, 3 or 4 (SwiGLU needs the gate/up PAIRS in one wave: even NTW; q/k/v and the residual
 // projections take any).  MT = 16-row tiles per workgroup (BM = 16 MT rows: 128, 64 or 32).  NW = 4 or 8 waves side by side: the
@@ -76,8 +92,19 @@ struct BigGemmParams {
 // row-per-register layout needed (the q stores alone were 10 us of an 80 us q/k/v launch, profiles/r04_prefill_knockout_qkv_stores.json);
 // RoPE partners (8 columns apart in a tile) are lanes l and l ^ 32.  The V^T page ([d][slot]: consecutive SLOTS are contiguous) keeps
 // 2-byte stores: 16 lanes = 16 consecutive slots of one feature, the same 32-byte runs as before.
-template <int EPI, int NTW, int MT, int PB, int NW, bool PIN, int KS = 1, bool TR = true>
+//
+// WF = the weight format (lsk_gemm.h).  LSK_WF_FP8 (bf16 build only): p.wp is the packed FP8 buffer the decode kernels read, so an FP8
+// engine owns ONE set of projection buffers.  A k-step of a tile is 512 B and a ring slot 8 B; the 8 codes of a slot are widened to bf16
+// when the slot is consumed (once per K-tile and column tile, 8 VALU instructions, whatever MT) and go through the same MFMAs in the same
+// order -- same K-tile walk, same KS split, same TR operand swap.  The packed row's power of two multiplies the fp32 accumulator once,
+// after the K-split hand-off and in front of the epilogue's first rounding: a power of two commutes with every fp32 rounding of the
+// accumulation and with the addition of the two partial sums, so the output is bit for bit the LSK_WF_ELEM instance's on the dequantised
+// weights.  The scale table is in PACKED row order like the codes: index 16 tile + column in tile.
+template <int EPI, int NTW, int MT, int PB, int NW, bool PIN, int KS = 1, bool TR = true, int WF = LSK_WF_ELEM>
 __global__ __launch_bounds__(NW * KS * 64, 2) void lsk_gemm_big_kernel(const BigGemmParams p) {
+    static_assert(WF == LSK_WF_ELEM || (WF == LSK_WF_FP8 && LSK_ELEM_DTYPE == 0), "FP8 weight storage exists in the bf16 build only");
+    typedef typename lsk_big_slot<WF>::type slot_t;
+    constexpr int WB = (WF == LSK_WF_FP8) ? 1 : LSK_EB;     // bytes per packed weight element
     constexpr int BM = MT * 16;
     constexpr int SR = NW * 8;                  // rows staged per pass (8 lanes per row)
     constexpr int NP = BM / SR;                 // staging passes per K-tile
@@ -126,9 +153,22 @@ __global__ __launch_bounds__(NW * KS * 64, 2) void lsk_gemm_big_kernel(const Big
     // (last panel of a ragged N) streams the last valid tile instead and drops the result: every load of the K loop is
     // UNCONDITIONAL -- a "tile ok ? load : zero" select makes hipcc branch around each load and fall back to s_waitcnt vmcnt(0)
     // in front of the MFMAs (measured in the ISA: the prefetched tiles were drained every iteration).
-    const elem_t* bptr[NTW];
+    const unsigned char* bptr[NTW];
 #pragma unroll
-    for (int nt = 0; nt < NTW; ++nt) bptr[nt] = p.wp + ((size_t)min(T0 + nt, p.n_tiles - 1) * ksteps * 64 + lane) * 8;
+    for (int nt = 0; nt < NTW; ++nt) bptr[nt] = (const unsigned char*)p.wp + ((size_t)min(T0 + nt, p.n_tiles - 1) * ksteps * 64 + lane) * (8 * WB);
+    // FP8 weights: the powers of two of this lane's accumulator columns, requested in front of the ring from clamped (always valid) tile
+    // indices -- transposed: four consecutive packed rows per column tile (one 16-byte load), row-per-register: column lane % 16
+    [[maybe_unused]] f32x4 sc4[NTW];
+    [[maybe_unused]] float sc1[NTW];
+    if constexpr (WF == LSK_WF_FP8) {
+        const float* wscale = (const float*)((const unsigned char*)p.wp + (size_t)p.n_tiles * 16 * p.K);
+#pragma unroll
+        for (int nt = 0; nt < NTW; ++nt) {
+            const float* sp = wscale + min(T0 + nt, p.n_tiles - 1) * 16;
+            if (TR) sc4[nt] = *(const f32x4*)(sp + (lane >> 4) * 4);
+            else sc1[nt] = sp[lane & 15];
+        }
+    }
 
     f32x4 acc[MT][NTW];
 #pragma unroll
@@ -140,7 +180,7 @@ __global__ __launch_bounds__(NW * KS * 64, 2) void lsk_gemm_big_kernel(const Big
     // two register sets (tiles kt+1, kt+2) feeding the double-buffered LDS image.  Slot indices are static: the K loop is
     // unrolled by the ring depth, every load is unconditional, so every s_waitcnt in the loop is a COUNTED one.
     elem8 aq[2][NP];
-    elem8 bq[PB][NTW][2];
+    slot_t bq[PB][NTW][2];
     auto load_a = [&](int kt, elem8 (&dst)[NP]) {
 #pragma unroll
         for (int i = 0; i < NP; ++i) dst[i] = *(const elem8*)(aptr_i[i] + (size_t)(kt * KS + grp) * LSK_BIG_BK);
@@ -149,12 +189,12 @@ __global__ __launch_bounds__(NW * KS * 64, 2) void lsk_gemm_big_kernel(const Big
 #pragma unroll
         for (int i = 0; i < NP; ++i) *(elem8*)(awr_i[i] + buf * (BM * LSK_BIG_LDA)) = src[i];
     };
-    auto load_b = [&](int kt, elem8 (&dst)[NTW][2]) {
+    auto load_b = [&](int kt, slot_t (&dst)[NTW][2]) {
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            const size_t bo = (size_t)((kt * KS + grp) * 2 + s) * 512;
+            const size_t bo = (size_t)((kt * KS + grp) * 2 + s) * (512 * WB);
 #pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) dst[nt][s] = *(const elem8*)(bptr[nt] + bo);
+            for (int nt = 0; nt < NTW; ++nt) dst[nt][s] = *(const slot_t*)(bptr[nt] + bo);
         }
     };
     // nkt is a multiple of PB (the host picks PB accordingly); indices past the end are clamped to the last
@@ -179,12 +219,15 @@ __global__ __launch_bounds__(NW * KS * 64, 2) void lsk_gemm_big_kernel(const Big
             const unsigned char* abase = ard + cur * (BM * LSK_BIG_LDA);
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
+                elem8 bf[NTW];                                // (LSK_WF_ELEM: the ring slots themselves)
+#pragma unroll
+                for (int nt = 0; nt < NTW; ++nt) bf[nt] = lsk_big_frag(bq[u][nt][s]);
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
                     const elem8 a = *(const elem8*)(abase + mt * 16 * LSK_BIG_LDA + s * (32 * LSK_EB));
 #pragma unroll
                     for (int nt = 0; nt < NTW; ++nt)
-                        acc[mt][nt] = TR ? LSK_MFMA_16x16x32(bq[u][nt][s], a, acc[mt][nt], 0, 0, 0) : LSK_MFMA_16x16x32(a, bq[u][nt][s], acc[mt][nt], 0, 0, 0);
+                        acc[mt][nt] = TR ? LSK_MFMA_16x16x32(bf[nt], a, acc[mt][nt], 0, 0, 0) : LSK_MFMA_16x16x32(a, bf[nt], acc[mt][nt], 0, 0, 0);
                 }
             }
             load_b(min(kt + PB, last), bq[u]);                // refill the slot just consumed
@@ -210,6 +253,15 @@ __global__ __launch_bounds__(NW * KS * 64, 2) void lsk_gemm_big_kernel(const Big
             for (int nt = 0; nt < NTW; ++nt) acc[mt][nt] += xch[((w * MT + mt) * NTW + nt) * 64 + lane];
     }
     if (!tile_ok) return;
+    if constexpr (WF == LSK_WF_FP8) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NTW; ++nt) {
+                if (TR) acc[mt][nt] *= sc4[nt];
+                else acc[mt][nt] *= sc1[nt];
+            }
+    }
 
     const int c16 = lane & 15;
     const int rg = lane >> 4;

@@ -108,10 +108,10 @@ class HipEngine:
             raise _lib.LskError(f"weight_format={weight_format!r} needs a bf16 model; this one is {dtype_name} "
                                 "(FP8 weight storage exists in the bf16 build only)")
         self.weight_format = weight_format
-        # what the MFMA-tiled prefill kernels read under FP8: bf16-packed copies of the DEQUANTISED projections (same values as the codes,
-        # so prompt KV and exit hiddens are the bf16 engine's on the dequantised model; packed bytes are 1.5 x bf16's instead of 0.5 x,
-        # DESIGN.md 3.1).  None in the default format: one set of buffers serves both paths.
-        self.prefill_weights = "bf16_copy_of_dequantized" if weight_format == "fp8_e4m3" else None
+        # what the MFMA-tiled prefill kernels read under FP8: the same codes as the decode kernels (their FP8 instances widen them in
+        # the weight ring and scale the accumulators, csrc/lsk_gemm_big.h), so prompt KV and exit hiddens are the bf16 engine's on the
+        # dequantised model and packed bytes are 0.5 x bf16's.  None in the default format.  One set of buffers serves both paths.
+        self.prefill_weights = "fp8_codes" if weight_format == "fp8_e4m3" else None
         self.lib = _lib.load(dtype=dtype_name)
         self.elem_bytes = torch.empty(0, dtype=self.dtype).element_size()
         # sample=True on the device: the sampler's 16-bit logit keys are exact at bf16 / fp16 only (lsk_key16, lsk_sample.h).  Over fp32
@@ -145,7 +145,7 @@ class HipEngine:
         self.release_weights = release_weights
         self._handle = ctypes.c_void_p(None)
         self._packed = []           # per-layer packed buffers (kept alive); None outside layer_range
-        self._packed_prefill = []   # FP8 format: per-layer (wqkv, wo, wgu, wdown) bf16-packed dequantised copies for the prefill kernels
+        self._packed_prefill = {}   # measurement only (_bind_prefill_copies): layer -> bf16-packed dequantised copies for the prefill kernels
         self._globals = {}
         self._buffers = {}
         self._options = {}          # lsk_engine_set_option values, re-applied whenever the C engine is recreated
@@ -209,8 +209,8 @@ class HipEngine:
         if self.release_weights:
             raise _lib.LskError("refresh_weights: this engine released the original weights (release_weights=True)")
         with torch.cuda.device(self.device):
+            self._bind_prefill_copies(list(self._packed_prefill), bind=False)      # (copies of the old values, if a tool bound any)
             self._packed = []
-            self._packed_prefill = []
             self._globals = {}
             self._pack_weights(model)
             self._bind_weights()
@@ -225,41 +225,66 @@ class HipEngine:
     def _fp8(self) -> bool:
         return self.weight_format == "fp8_e4m3"
 
-    def _packed_buffer(self, n_rows: int, k: int, prefill_copy: bool = False):
-        """The packed buffer of an [n_rows][k] projection in the engine's weight format.  FP8: a (buffer, rows, prefill) triple --
-        the FP8 buffer, its rows (which locate the scale table) and, with `prefill_copy`, the bf16-packed buffer of the dequantised
-        weights the prefill kernels read."""
+    def _packed_buffer(self, n_rows: int, k: int, fp8: bool):
+        """The packed buffer of an [n_rows][k] projection (FP8: the codes, then one fp32 power of two per packed row)."""
         nbytes = ctypes.c_size_t(0)
-        if not self._fp8:
-            self._ck(self.lib.lsk_packed_bytes(n_rows, k, ctypes.byref(nbytes)))
-            return torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-        self._ck(self.lib.lsk_packed_bytes_fp8(n_rows, k, ctypes.byref(nbytes)))
-        buf = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-        pf = None
-        if prefill_copy:
-            self._ck(self.lib.lsk_packed_bytes(n_rows, k, ctypes.byref(nbytes)))
-            pf = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-        return (buf, _round_up(n_rows, 16), pf)
+        self._ck((self.lib.lsk_packed_bytes_fp8 if fp8 else self.lib.lsk_packed_bytes)(n_rows, k, ctypes.byref(nbytes)))
+        return torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
 
-    def _pack_into(self, dst, w: torch.Tensor, tile_offset: int, tile_stride: int, rope_hd: int) -> None:
+    def _pack_into(self, dst, w: torch.Tensor, tile_offset: int, tile_stride: int, rope_hd: int, fp8: bool) -> None:
         w = w.detach()
         if w.dtype != self.dtype or w.device != self.device:
             raise _lib.LskError(f"all projection weights must be {self.dtype} on the engine's device")
         if w.stride(1) != 1:
             w = w.contiguous()
-        if not self._fp8:
+        if not fp8:
             self._ck(self.lib.lsk_pack_linear(w.data_ptr(), w.shape[0], w.shape[1], w.stride(0), dst.data_ptr(),
                                            tile_offset, tile_stride, rope_hd, self._stream))
             return
-        buf, rows, pf = dst
-        self._ck(self.lib.lsk_pack_linear_fp8(w.data_ptr(), w.shape[0], w.shape[1], w.stride(0), buf.data_ptr(), rows,
+        rows = dst.numel() // (w.shape[1] + 4)       # packed rows of the destination: they locate its scale table
+        self._ck(self.lib.lsk_pack_linear_fp8(w.data_ptr(), w.shape[0], w.shape[1], w.stride(0), dst.data_ptr(), rows,
                                            tile_offset, tile_stride, rope_hd, self._stream))
-        if pf is not None:
-            from . import quant
-            d = quant.dequantize_weight(w)           # (the format's specification, run on the device; the device quantiser agrees bit for bit)
-            self._ck(self.lib.lsk_pack_linear(d.data_ptr(), d.shape[0], d.shape[1], d.stride(0), pf.data_ptr(),
-                                           tile_offset, tile_stride, rope_hd, self._stream))
-            torch.cuda.current_stream(self.device).synchronize()     # `d` is a temporary: the pack kernel must be through with it
+
+    def _pack_projections(self, layer, fp8: bool, values=lambda w: w):
+        """(wqkv, wo, wgu, wdown) of one decoder layer, packed: q|k|v concatenated (q and k in RoPE row order), gate / up interleaved by
+        tile.  `values` maps a weight to what is packed in its place."""
+        hd, H, I = self.head_dim, self.hidden, self.intermediate
+        qdim, kvdim = self.n_heads * hd, self.n_kv_heads * hd
+        a, mlp = layer.self_attn, layer.mlp
+        plan = ((qdim + 2 * kvdim, H, ((a.q_proj, 0, 1, hd), (a.k_proj, qdim // 16, 1, hd), (a.v_proj, (qdim + kvdim) // 16, 1, 0))),
+                (H, qdim, ((a.o_proj, 0, 1, 0),)),
+                (2 * I, H, ((mlp.gate_proj, 0, 2, 0), (mlp.up_proj, 1, 2, 0))),
+                (H, I, ((mlp.down_proj, 0, 1, 0),)))
+        out = []
+        for n_rows, k, parts in plan:
+            buf = self._packed_buffer(n_rows, k, fp8)
+            for lin, tile_offset, tile_stride, rope_hd in parts:
+                self._pack_into(buf, values(lin.weight), tile_offset, tile_stride, rope_hd, fp8)
+            out.append(buf)
+        return tuple(out)
+
+    def packed_weight_bytes(self) -> dict:
+        """Bytes of the packed projection buffers (this engine's layers and its lm_head): "decode" -- the buffers the decode path reads,
+        which in either weight format are the ones prefill reads too; "prefill_only" -- buffers that only the prefill kernels read (0)."""
+        bufs = [t for pk in self._packed if pk is not None for t in pk[:4]]
+        bufs += [self._globals["lm_head"]] if self._globals.get("lm_head") is not None else []
+        return {"decode": sum(t.numel() for t in bufs),
+                "prefill_only": sum(t.numel() for pk in self._packed_prefill.values() for t in pk)}
+
+    def _bind_prefill_copies(self, layers=None, bind: bool = True) -> None:
+        """A/B lever of tools/ and tests/, FP8 engines only: bf16-packed copies of the DEQUANTISED projections of `layers` (default: all of
+        this engine's), bound with lsk_engine_set_layer_prefill, so that those layers prefill through the model-dtype kernels -- what
+        every FP8 engine did before the prefill kernel read the codes.  bind=False unbinds and frees them."""
+        from . import quant
+        for i in (range(*self.layer_range) if layers is None else layers):
+            if bind:
+                self._packed_prefill[i] = self._pack_projections(self.model.model.layers[i], False, quant.dequantize_weight)
+                torch.cuda.synchronize(self.device)          # the dequantised values are temporaries: the pack kernels must be through
+                ptrs = [t.data_ptr() for t in self._packed_prefill[i]]
+            else:
+                ptrs = [None] * 4
+                self._packed_prefill.pop(i, None)
+            self._ck(self.lib.lsk_engine_set_layer_prefill(self._handle, i, *ptrs))
 
     def unpacked_fp8(self, layer: int, name: str):
         """(codes uint8 [rows][k], scale fp32 [rows]) of a packed FP8 buffer in PACKED row order (quant.unpack_tiles); name: wqkv | wo |
@@ -274,32 +299,15 @@ class HipEngine:
         return quant.unpack_tiles(buf, *shapes[name])
 
     def _pack_weights(self, m) -> None:
-        hd, H, I = self.head_dim, self.hidden, self.intermediate
-        qdim, kvdim = self.n_heads * hd, self.n_kv_heads * hd
+        H = self.hidden
         for idx, layer in enumerate(m.model.layers):
             if not (self.layer_range[0] <= idx < self.layer_range[1]):
                 self._packed.append(None)       # another pipeline rank owns this layer
-                if self._fp8:
-                    self._packed_prefill.append(None)
                 continue
             a, mlp = layer.self_attn, layer.mlp
-            wqkv = self._packed_buffer(qdim + 2 * kvdim, H, prefill_copy=True)
-            self._pack_into(wqkv, a.q_proj.weight, 0, 1, hd)
-            self._pack_into(wqkv, a.k_proj.weight, qdim // 16, 1, hd)
-            self._pack_into(wqkv, a.v_proj.weight, (qdim + kvdim) // 16, 1, 0)
-            wo = self._packed_buffer(H, qdim, prefill_copy=True)
-            self._pack_into(wo, a.o_proj.weight, 0, 1, 0)
-            wgu = self._packed_buffer(2 * I, H, prefill_copy=True)
-            self._pack_into(wgu, mlp.gate_proj.weight, 0, 2, 0)
-            self._pack_into(wgu, mlp.up_proj.weight, 1, 2, 0)
-            wdown = self._packed_buffer(H, I, prefill_copy=True)
-            self._pack_into(wdown, mlp.down_proj.weight, 0, 1, 0)
             n1 = layer.input_layernorm.weight.detach().contiguous()
             n2 = layer.post_attention_layernorm.weight.detach().contiguous()
-            if self._fp8:
-                self._packed_prefill.append(tuple(t[2] for t in (wqkv, wo, wgu, wdown)))
-                wqkv, wo, wgu, wdown = (t[0] for t in (wqkv, wo, wgu, wdown))
-            self._packed.append((wqkv, wo, wgu, wdown, n1, n2))
+            self._packed.append(self._pack_projections(layer, self._fp8) + (n1, n2))
             if self.release_weights:
                 torch.cuda.synchronize(self.device)
                 for lin in (a.q_proj, a.k_proj, a.v_proj, a.o_proj, mlp.gate_proj, mlp.up_proj, mlp.down_proj):
@@ -309,9 +317,9 @@ class HipEngine:
         have_head, have_embed = not m.lm_head.weight.is_meta, not m.model.embed_tokens.weight.is_meta
         self._globals["lm_head"] = None
         if have_head:
-            head = self._packed_buffer(self.vocab, H)
-            self._pack_into(head, m.lm_head.weight, 0, 1, 0)
-            self._globals["lm_head"] = head[0] if self._fp8 else head      # (no prefill copy: the head is a decode-path launch)
+            head = self._packed_buffer(self.vocab, H, self._fp8)
+            self._pack_into(head, m.lm_head.weight, 0, 1, 0, self._fp8)
+            self._globals["lm_head"] = head
             tied = have_embed and m.lm_head.weight.data_ptr() == m.model.embed_tokens.weight.data_ptr()
             if self.release_weights and not tied:
                 torch.cuda.synchronize(self.device)
@@ -375,7 +383,7 @@ class HipEngine:
             wqkv, wo, wgu, wdown, n1, n2 = packed
             self._ck(self.lib.lsk_engine_set_layer(handle, i, wqkv.data_ptr(), wo.data_ptr(), wgu.data_ptr(),
                                                 wdown.data_ptr(), n1.data_ptr(), n2.data_ptr()))
-            if self._fp8:
+            if i in self._packed_prefill:           # (a recreated C engine keeps the copies _bind_prefill_copies bound)
                 self._ck(self.lib.lsk_engine_set_layer_prefill(handle, i, *[t.data_ptr() for t in self._packed_prefill[i]]))
         g = self._globals
         ptr = lambda t: t.data_ptr() if t is not None else None          # noqa: E731 -- NULL: not bound on this rank

@@ -65,8 +65,7 @@ def leg(model, kw, prompt, eos, a):
         "ms_per_step": round(1e3 * a.steps / med / steps, 4), "kernel_table": table, "algorithmic_bytes": stream_bytes,
         "floor_fraction": round(stream_bytes / HBM_PEAK / (a.steps / med), 4), "ar_tokens_per_s": round(ar_rates[0], 2),
         "projection_bytes": eng.projection_bytes(),
-        "packed_bytes": sum(t.numel() for pk in eng._packed if pk is not None for t in pk[:4]) + eng._globals["lm_head"].numel(),
-        "prefill_copy_bytes": sum(t.numel() for pk in eng._packed_prefill if pk is not None for t in pk),
+        "packed_bytes": eng.packed_weight_bytes()["decode"], "prefill_copy_bytes": eng.packed_weight_bytes()["prefill_only"],
     }, res.predicted_tokens, ar.predicted_tokens, eng
 
 
