@@ -7,6 +7,7 @@
 #include "lsk_engine.h"
 #include "lsk_gemm_big.h"
 #include "lsk_launch.h"
+#include "lsk_launch_big.h"
 #include "lsk_small.h"
 
 extern "C" const char* lsk_last_error(void) { return g_err; }
@@ -499,146 +500,27 @@ int lsk_embed_rows_dev(lsk_engine* e, const int* tokens_dev, int n, elem_t* dst,
     return 0;
 }
 
-// Prefill tile shapes (lsk_gemm_big.h): NTW 16-column tiles per wave x MT 16-row tiles per workgroup x NW waves, weight ring PB
-// K-tiles deep, KS K-split groups per workgroup, TR = transposed product (8-byte epilogue accesses).  Chosen per projection and prompt
-// length from kernel times at 127 .. 4095 rows (tools/gemm_big_bench.hip, profiles/r06_gemm_big_bench*.txt):
-//   gate/up     : 128 x 128 tile, ring 2 (164 registers: three waves per SIMD; ring 4 holds two); NOT transposed (the SwiGLU epilogue
-//                 is a quarter of q/k/v's stores and the swapped operand order measures 4 % slower in the main loop); the best or within
-//                 2 % of it at every prompt length from 383 rows on;
-//   q/k/v       : transposed; 64 x 128 -> 64 x 192 -> 128 x 192 -> 128 x 256 / 128 x 384 (eight waves) as the prompt grows, by a cost
-//                 model of rounds x tile area (launch_big_qkv);
-//   o_proj/down : K-split 2 with 32- / 64- / 128-row tiles while that is <= one workgroup per CU, 128 x 256 (eight waves) or 128 x 128
-//                 above (launch_big_resid).
-// WF = the weight format of p.wp.  The rules are functions of the projection and the prompt length alone: the FP8 instances take the SAME
-// shape, ring depth and K-split as the model-dtype ones (same K order: the bit-identity of the two formats rests on it).
-template <int EPI, int NTW, int MT, int PB, int NW, bool PIN, int KS, bool TR, int WF>
-static int launch_big_pb(BigGemmParams& p, hipStream_t st) {
-    const int rb = (p.M + MT * 16 - 1) / (MT * 16);                        // row blocks
-    const int panels = (p.n_tiles + NW * NTW - 1) / (NW * NTW);            // weight panels of NW * NTW tiles
-    const dim3 grid(rb * 8 * ((panels + 7) / 8));                          // XCD-aware 1-D map: lsk_gemm_big.h
-    hipLaunchKernelGGL((lsk_gemm_big_kernel<EPI, NTW, MT, PB, NW, PIN, KS, TR, WF>), grid, dim3(NW * KS * 64), 0, st, p);
-    HIP_OK(hipGetLastError());
-    return 0;
+// What a layer's prefill launches read: the model-dtype copies of its dequantised projections where the caller bound them
+// (lsk_engine_set_layer_prefill: optional, FP8 weight format), read by the model-dtype instances; otherwise the buffers the decode
+// kernels read, in the engine's format (FP8: the FP8 instances read the codes)
+struct PrefillWeights { const elem_t *wqkv, *wo, *wgu, *wdown; int wfmt; };
+static PrefillWeights prefill_weights(const lsk_engine* e, const LayerWeights& lw) {
+    if (lw.pf_wqkv != nullptr) return {lw.pf_wqkv, lw.pf_wo, lw.pf_wgu, lw.pf_wdown, LSK_WF_ELEM};
+    return {lw.wqkv, lw.wo, lw.wgu, lw.wdown, e->weight_format == LSK_WEIGHT_FORMAT_FP8_E4M3 ? LSK_WF_FP8 : LSK_WF_ELEM};
 }
 
-// PB = the deepest weight ring of {PBMAX, 2} that divides the number of K-tiles of a K-split group (K is a multiple of 128: run_bulk)
-template <int WF, int EPI, int NTW, int MT, int PBMAX, int NW, bool PIN, int KS = 1, bool TR = true>
-static int launch_big(BigGemmParams& p, hipStream_t st) {
-    const int nkt = p.K / LSK_BIG_BK / KS;
-    if constexpr (PBMAX == 4) {          // (constexpr: a ring-4 form of a ring-2 shape must not even be instantiated -- some would spill)
-        if (nkt % 4 == 0) return launch_big_pb<EPI, NTW, MT, 4, NW, PIN, KS, TR, WF>(p, st);
-    }
-    return launch_big_pb<EPI, NTW, MT, 2, NW, PIN, KS, TR, WF>(p, st);
-}
-
-// the instance of a shape rule for the format of p.wp (the FP8 instances exist in the bf16 build only)
-#if LSK_ELEM_DTYPE == 0
-#define LSK_BIG_BY_FORMAT(rule, p, st) \
-    ((p).wfmt == LSK_WF_FP8 ? rule<LSK_WF_FP8>(p, st) : (p).wfmt == LSK_WF_ELEM ? rule<LSK_WF_ELEM>(p, st) : lsk_fail("prefill: unknown weight format %d", (p).wfmt))
-#else
-#define LSK_BIG_BY_FORMAT(rule, p, st) \
-    ((p).wfmt == LSK_WF_ELEM ? rule<LSK_WF_ELEM>(p, st) : lsk_fail("prefill: FP8 weight storage exists in the bf16 library only"))
-#endif
-
-// Tile shape per launch from the WORKGROUP COUNTS each shape would give (round 6, second pass: tools/gemm_big_bench.hip with
-// LSK_BENCH_EXPLORE=1 at 127 .. 4095 rows, profiles/r06_gemm_big_bench_explore.txt).  A CU sustains ~3.5 TFLOP/s on these kernels once it
-// holds two waves per SIMD, whatever the tile, so the choice is about balance: the biggest tile that still gives every CU work, and never a
-// count that leaves half the chip a second round to itself (128 x 256 at 1023 rows of a 12 288-feature q/k/v: 384 workgroups at one per
-// CU, 133 us against 114 for 512 workgroups of 128 x 192).
-template <int WF>
-static int launch_big_qkv_wf(BigGemmParams& p, hipStream_t st) {
-#if LSK_EB == 4
-    return launch_big<WF, EPI_QKV, 2, 4, 2, 4, false>(p, st);   // fp32: one 64 x 128 shape (twice the fragment registers: the larger tiles would spill)
-#else
-    // cost of a shape = (workgroups on the busiest CU) x (tile area) / (TFLOP/s a CU sustains on that shape), the rates read off the table:
-    // ~3.7-3.8 for the eight-wave tiles, 3.45 for 128-row four-wave tiles once a CU holds two of them (2.85 alone: one wave per SIMD),
-    // 2.2-2.8 for 64-row tiles.  llama2-7B (N = 12 288): 64 x 128 up to 191 rows, 64 x 192 to 319, 128 x 192 to 639, 128 x 384 where it is
-    // whole rounds (1023 rows: 256 workgroups, 147.1 -> 102.3 us = 1 006 TFLOP/s; 2047: 512, 260.6 -> 211.0), 128 x 256 / 128 x 192 between.
-    struct Shape { int bm, tiles; float alone, shared; };
-    static const Shape shapes[5] = {{64, 8, 1.75f, 2.3f}, {64, 12, 2.15f, 2.8f}, {128, 12, 2.85f, 3.45f}, {128, 16, 3.7f, 3.7f}, {128, 24, 3.8f, 3.8f}};
-    int best = 0;
-    float best_cost = 0.f;
-    for (int i = 0; i < 5; ++i) {
-        const Shape& sh = shapes[i];
-        const int wgs = ((p.M + sh.bm - 1) / sh.bm) * ((p.n_tiles + sh.tiles - 1) / sh.tiles);
-        const int per_cu = (wgs + 255) / 256;
-        float rate = per_cu == 1 ? sh.alone : sh.shared;
-        if (i == 0 && per_cu >= 3) rate = 2.65f;
-        const float cost = (float)per_cu * (float)(sh.bm * sh.tiles) / rate;
-        if (i == 0 || cost <= best_cost) { best = i; best_cost = cost; }        // ties go to the bigger tile
-    }
-    switch (best) {
-        case 4: return launch_big<WF, EPI_QKV, 3, 8, 2, 8, true>(p, st);
-        case 3: return launch_big<WF, EPI_QKV, 2, 8, 2, 8, false>(p, st);
-        case 2: return launch_big<WF, EPI_QKV, 3, 8, 2, 4, false>(p, st);
-        case 1: return launch_big<WF, EPI_QKV, 3, 4, 2, 4, false>(p, st);
-        default: return launch_big<WF, EPI_QKV, 2, 4, 2, 4, false>(p, st);
-    }
-#endif
-}
-static int launch_big_qkv(BigGemmParams& p, hipStream_t st) { return LSK_BIG_BY_FORMAT(launch_big_qkv_wf, p, st); }
-
-template <int WF>
-static int launch_big_gateup_wf(BigGemmParams& p, hipStream_t st) {
-#if LSK_EB == 4
-    return launch_big<WF, EPI_SWIGLU, 2, 4, 2, 4, false, 1, false>(p, st);
-#else
-    return launch_big<WF, EPI_SWIGLU, 2, 8, 2, 4, false, 1, false>(p, st);
-#endif
-}
-static int launch_big_gateup(BigGemmParams& p, hipStream_t st) { return LSK_BIG_BY_FORMAT(launch_big_gateup_wf, p, st); }
-
-template <int WF>
-static int launch_big_resid_wf(BigGemmParams& p, hipStream_t st) {
-#if LSK_EB == 4
-    return launch_big<WF, EPI_RESID, 2, 4, 2, 4, false>(p, st);
-#else
-    const int panels = (p.n_tiles + 7) / 8;
-    const int rb128 = (p.M + 127) / 128;
-    // N = hidden is few panels: while a shape gives <= one workgroup per CU, K-split 2 (eight waves per workgroup, the two halves of K side
-    // by side: two waves per SIMD instead of one) with the SMALLEST row tile that still does -- 32 rows up to 255 prompt rows of a
-    // 4096-wide model (down 67.5 -> 58.2 us), 64 up to 511 (round 6, first pass), 128 up to 1023 (down 135.5 -> 106.3).  The two groups
-    // need an even number of ring-depth-2 K-tile pairs each: K a multiple of 256.
-    if ((p.K / LSK_BIG_BK) % 4 == 0) {
-        if (((p.M + 31) / 32) * panels <= 256) return launch_big<WF, EPI_RESID, 2, 2, 2, 4, false, 2>(p, st);
-        if (((p.M + 63) / 64) * panels <= 256) return launch_big<WF, EPI_RESID, 2, 4, 2, 4, true, 2>(p, st);
-        if (rb128 * panels <= 256) return launch_big<WF, EPI_RESID, 2, 8, 2, 4, false, 2>(p, st);
-    }
-    // beyond that 128 x 256 tiles of eight waves (pinned activation requests) wherever their count is at most one round or at least two
-    // (2047 rows: o_proj 72.6 -> 65.0 us, down 218.9 -> 183.1), 128 x 128 in between (3071 rows: 384 of them would leave half the chip a
-    // second round)
-    const int w256 = rb128 * ((p.n_tiles + 15) / 16);
-    if (rb128 * panels > 256 && (w256 <= 256 || w256 >= 512)) return launch_big<WF, EPI_RESID, 2, 8, 2, 8, true>(p, st);
-    if (rb128 * panels >= 512) return launch_big<WF, EPI_RESID, 2, 8, 2, 4, false>(p, st);
-    return launch_big<WF, EPI_RESID, 2, 4, 4, 4, true>(p, st);
-#endif
-}
-static int launch_big_resid(BigGemmParams& p, hipStream_t st) { return LSK_BIG_BY_FORMAT(launch_big_resid_wf, p, st); }
-
-// Prompt rows [0, n) of the bulk buffer through layers [lb, le) with the MFMA-tiled prefill kernels.
+// Prompt rows [0, n) of the bulk buffer through layers [lb, le) with the MFMA-tiled prefill kernels (lsk_launch_big.h).
 static int run_bulk_big(lsk_engine* e, int n, int lb, int le, hipStream_t st) {
     const lsk_config& c = e->cfg;
     const int qdim = c.n_heads * c.head_dim;
-    const int kvdim = c.n_kv_heads * c.head_dim;
     const int* kvp = &e->state->kv_len;
     for (int l = lb; l < le; ++l) {
         const LayerWeights& lw = e->layers[l];
-        // FP8 weight format: the FP8 instances read the codes the decode kernels read; a layer with model-dtype copies of its
-        // dequantised projections bound (lsk_engine_set_layer_prefill: optional) reads those with the model-dtype instances instead
-        const bool pf = lw.pf_wqkv != nullptr;
-        const int wfmt = (e->weight_format == LSK_WEIGHT_FORMAT_FP8_E4M3 && !pf) ? LSK_WF_FP8 : LSK_WF_ELEM;
+        const PrefillWeights w = prefill_weights(e, lw);
         elem_t* kpool = e->kv_pool + (size_t)l * e->kv_layer_elems;
         elem_t* vpool = kpool + e->kv_half_elems;
-        hipLaunchKernelGGL(lsk_rmsnorm_rows_kernel, dim3(n), dim3(256), 0, st, e->hbulk, c.hidden, lw.norm1, c.rms_eps, c.hidden, e->xn_bulk, c.hidden);
-        HIP_OK(hipGetLastError());
-        {
-            BigGemmParams p{};
-            p.x = e->xn_bulk; p.ldx = c.hidden; p.M = n; p.K = c.hidden; p.wp = pf ? lw.pf_wqkv : lw.wqkv; p.N = qdim + 2 * kvdim; p.n_tiles = p.N / 16; p.wfmt = wfmt;
-            p.q_out = e->q_bulk; p.ldq = qdim; p.kpool = kpool; p.vpool = vpool; p.block_table = e->block_table; p.page_size = c.page_size;
-            p.n_heads = c.n_heads; p.n_kv = c.n_kv_heads; p.head_dim = c.head_dim; p.rope_cos = e->rope_cos; p.rope_sin = e->rope_sin;
-            p.kv_len = kvp; p.pos_off = 0;
-            LSK_TRY(launch_big_qkv(p, st));
-        }
+        LSK_TRY(launch_rmsnorm_rows(c, e->hbulk, n, lw.norm1, e->xn_bulk, st));
+        LSK_TRY(launch_big_qkv(big_qkv(c, e->xn_bulk, n, w.wqkv, e->rope_cos, e->rope_sin, kvp, 0, e->block_table, e->q_bulk, kpool, vpool, w.wfmt), st));
         if (e->flash_prefill) {
             LSK_TRY(launch_attn_prefill(c, e->q_bulk, e->attn_bulk, kpool, vpool, e->block_table, kvp, 0, n, st));
         } else {
@@ -647,26 +529,10 @@ static int run_bulk_big(lsk_engine* e, int n, int lb, int le, hipStream_t st) {
                 LSK_TRY(launch_attn(e, e->q_bulk + (size_t)r0 * qdim, e->attn_bulk + (size_t)r0 * qdim, kpool, vpool, m, r0, st));
             }
         }
-        {
-            BigGemmParams p{};
-            p.x = e->attn_bulk; p.ldx = qdim; p.M = n; p.K = qdim; p.wp = pf ? lw.pf_wo : lw.wo; p.N = c.hidden; p.n_tiles = p.N / 16; p.wfmt = wfmt;
-            p.h = e->hbulk; p.ldh = c.hidden;
-            LSK_TRY(launch_big_resid(p, st));
-        }
-        hipLaunchKernelGGL(lsk_rmsnorm_rows_kernel, dim3(n), dim3(256), 0, st, e->hbulk, c.hidden, lw.norm2, c.rms_eps, c.hidden, e->xn_bulk, c.hidden);
-        HIP_OK(hipGetLastError());
-        {
-            BigGemmParams p{};
-            p.x = e->xn_bulk; p.ldx = c.hidden; p.M = n; p.K = c.hidden; p.wp = pf ? lw.pf_wgu : lw.wgu; p.N = 2 * c.intermediate; p.n_tiles = p.N / 16; p.wfmt = wfmt;
-            p.act = e->act_bulk; p.ldact = c.intermediate;
-            LSK_TRY(launch_big_gateup(p, st));
-        }
-        {
-            BigGemmParams p{};
-            p.x = e->act_bulk; p.ldx = c.intermediate; p.M = n; p.K = c.intermediate; p.wp = pf ? lw.pf_wdown : lw.wdown; p.N = c.hidden; p.n_tiles = p.N / 16; p.wfmt = wfmt;
-            p.h = e->hbulk; p.ldh = c.hidden;
-            LSK_TRY(launch_big_resid(p, st));
-        }
+        LSK_TRY(launch_big_resid(big_resid(e->attn_bulk, n, qdim, w.wo, c.hidden, e->hbulk, w.wfmt), st));
+        LSK_TRY(launch_rmsnorm_rows(c, e->hbulk, n, lw.norm2, e->xn_bulk, st));
+        LSK_TRY(launch_big_gateup(big_swiglu(c, e->xn_bulk, n, w.wgu, e->act_bulk, w.wfmt), st));
+        LSK_TRY(launch_big_resid(big_resid(e->act_bulk, n, c.intermediate, w.wdown, c.hidden, e->hbulk, w.wfmt), st));
     }
     return 0;
 }
@@ -674,10 +540,7 @@ static int run_bulk_big(lsk_engine* e, int n, int lb, int le, hipStream_t st) {
 // rows [0, n) of the bulk buffer (already embedded or holding exit hiddens) through layers [lb, le):
 // MFMA-tiled prefill kernels for real prompts, 16-row passes of the decode kernels for short ones.
 int lsk_run_bulk_dev(lsk_engine* e, int n, const int* base_ptr, int lb, int le, hipStream_t st) {
-    const lsk_config& c = e->cfg;
-    const int kq = LSK_BIG_BK * 2;               // the prefill kernel walks K in runs of >= 2 tiles
-    const bool big_ok = (c.hidden % kq == 0) && ((c.n_heads * c.head_dim) % kq == 0) && (c.intermediate % kq == 0);
-    if (n >= e->big_threshold && big_ok) return run_bulk_big(e, n, lb, le, st);
+    if (n >= e->big_threshold && big_gemm_ok(e->cfg)) return run_bulk_big(e, n, lb, le, st);
     for (int r0 = 0; r0 < n; r0 += LSK_MAX_ROWS) {
         const int m = (n - r0) < LSK_MAX_ROWS ? (n - r0) : LSK_MAX_ROWS;
         LSK_TRY(lsk_run_layers_dev(e, e->hbulk + (size_t)r0 * e->cfg.hidden, m, base_ptr, r0, lb, le, st));

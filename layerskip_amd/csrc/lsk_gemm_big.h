@@ -8,7 +8,7 @@
 // tiles: NTW = 2 is exactly one gate/up pair or one RoPE tile pair), one barrier per K-tile.  The block id is mapped
 // XCD-aware (see the kernel): the row blocks that share a weight panel run on ONE XCD, so the panel is fetched from
 // HBM once and re-read from that XCD's L2.  The host picks (NTW, MT, PB, NW, KS, TR) per projection and prompt length
-// (lsk_engine.hip, "Prefill tile shapes": by the workgroup count each shape would give); every shape without a K-split walks K in the same
+// (lsk_launch_big.h, "Prefill tile shapes": by the workgroup count each shape would give); every shape without a K-split walks K in the same
 // order, so those outputs are bit-identical.
 // __launch_bounds__(threads, 2): without the min-waves bound hipcc budgets a 4-wave workgroup 512 registers per wave,
 // parks half of the weight ring in AGPRs and shuffles it back and forth (84 v_accvgpr moves per 128 MFMAs); with it
@@ -74,7 +74,7 @@ __device__ __forceinline__ elem8 lsk_big_frag(const elem8 f) { return f; }
 // at two or three waves per SIMD; (8, 4) needs 288 registers (one wave per SIMD, measured 2x slower).  Every A fragment read from LDS
 // feeds NTW MFMAs (one 1 KiB fragment read = 8 LDS cycles for 16 MFMA cycles, four SIMDs on one LDS); measured, that is NOT what bounds
 // the kernel: on every shape that compiles a CU sustains 3.5-3.9 TFLOP/s once it holds two waves per SIMD (profiles/
-// r06_gemm_big_bench_explore.txt), so the host picks the shape whose workgroup COUNT makes whole rounds on the 256 CUs (lsk_engine.hip).
+// r06_gemm_big_bench_explore.txt), so the host picks the shape whose workgroup COUNT makes whole rounds on the 256 CUs (lsk_launch_big.h).
 //
 // KS = K-split INSIDE the workgroup (round 6).  The N = hidden projections of a 512-row prompt are 256 workgroups of 64 x 128 for 256 CUs:
 // ONE 4-wave workgroup per CU, one wave per SIMD -- nothing to switch to while a wave waits for its fragments, its barrier or its LDS
@@ -100,6 +100,15 @@ __device__ __forceinline__ elem8 lsk_big_frag(const elem8 f) { return f; }
 // after the K-split hand-off and in front of the epilogue's first rounding: a power of two commutes with every fp32 rounding of the
 // accumulation and with the addition of the two partial sums, so the output is bit for bit the LSK_WF_ELEM instance's on the dequantised
 // weights.  The scale table is in PACKED row order like the codes: index 16 tile + column in tile.
+
+// The grid of a launch: the host's half of the XCD-aware block -> (row block, weight panel) map at the top of the kernel below -- RB x 8
+// ids per run of 8 panels, the last run padded.  (The comment above is the kernel's.)
+template <int NTW, int MT, int NW>
+constexpr int lsk_big_grid(int M, int n_tiles) {
+    const int rb = (M + MT * 16 - 1) / (MT * 16);                          // row blocks
+    const int panels = (n_tiles + NW * NTW - 1) / (NW * NTW);              // weight panels of NW * NTW tiles
+    return rb * 8 * ((panels + 7) / 8);
+}
 template <int EPI, int NTW, int MT, int PB, int NW, bool PIN, int KS = 1, bool TR = true, int WF = LSK_WF_ELEM>
 __global__ __launch_bounds__(NW * KS * 64, 2) void lsk_gemm_big_kernel(const BigGemmParams p) {
     static_assert(WF == LSK_WF_ELEM || (WF == LSK_WF_FP8 && LSK_ELEM_DTYPE == 0), "FP8 weight storage exists in the bf16 build only");

@@ -7,7 +7,8 @@
 //     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -o build/gemm_big_bench tools/gemm_big_bench.hip && ./build/gemm_big_bench [rows ...]
 //
 // The weights of NL = 4 "layers" are cycled through (404 MB each: a launch never finds its panel in the 256 MiB Infinity Cache, as in
-// the engine's layer loop).  Epilogues: the engine's own (RoPE + paged K / V^T append, SwiGLU, residual add).
+// the engine's layer loop).  Epilogues: the engine's own (RoPE + paged K / V^T append, SwiGLU, residual add).  Parameters and grid are the
+// engine's (csrc/lsk_launch_big.h); under each projection's heading stands the configuration the engine's shape rule picks at that row count.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -15,8 +16,11 @@
 
 #include <vector>
 
-#include "../layerskip_amd/csrc/lsk_gemm_big.h"
+#include "../layerskip_amd/csrc/lsk_launch_big.h"
 #include "../layerskip_amd/csrc/lsk_small.h"
+
+// the error convention of the shared launchers (lsk_host.h): here, print and exit
+int lsk_fail(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vprintf(fmt, ap); va_end(ap); printf("\n"); exit(1); }
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s (line %d)\n", #x, hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
 
@@ -28,21 +32,16 @@ __global__ void fill_kernel(elem_t* p, size_t n, unsigned seed, float scale) {
     }
 }
 
-__global__ void checksum_kernel(const unsigned short* p, size_t n, unsigned long long* out) {
-    unsigned long long acc = 0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) acc += (unsigned long long)p[i] * (2 * (i % 1000003) + 1);
-    atomicAdd(out, acc);
-}
-
 static const int NL = 4;
-static const int H = 4096, I = 11008, NH = 32, NKV = 32, HD = 128;
+static const int H = 4096, I = 11008, NH = 32, NKV = 32, HD = 128;      // llama2-7B
+static const int MAX_ROWS = 4096;
+static const lsk_config CFG = {NL, H, I, NH, NKV, HD, 32000, 1e-5f, MAX_ROWS + 128, 128, MAX_ROWS, 0};
 static int g_iters = 20;
 
 struct Bufs {
     elem_t *x, *act_in, *h, *act_out, *q, *kpool, *vpool, *cos, *sin;
     elem_t *wqkv[NL], *wo[NL], *wgu[NL], *wdown[NL];
     int *table, *kv_len;
-    unsigned long long* sum;
 };
 
 static elem_t* dalloc(size_t n) { elem_t* p; CK(hipMalloc(&p, n * sizeof(elem_t))); return p; }
@@ -61,22 +60,18 @@ static elem_t* packed_weight(int n_rows, int k, unsigned seed, int tile_stride, 
 template <int EPI, int NTW, int MT, int PB, int NW, bool PIN, int KS, bool TR = true>
 static float run_cfg(const char* name, BigGemmParams p, const elem_t* const* weights, elem_t* out, size_t out_elems, const elem_t* restore, Bufs& b,
                      std::vector<unsigned short>* first, double flops) {
-    const int rb = (p.M + MT * 16 - 1) / (MT * 16);
-    const int panels = (p.n_tiles + NW * NTW - 1) / (NW * NTW);
-    const dim3 grid(rb * 8 * ((panels + 7) / 8));
+    const dim3 grid(lsk_big_grid<NTW, MT, NW>(p.M, p.n_tiles));
     if ((p.K / LSK_BIG_BK / KS) % PB) { printf("  %-44s skipped (K-tiles per group not a multiple of the ring depth)\n", name); return 0.f; }
     hipEvent_t a, e;
     CK(hipEventCreate(&a)); CK(hipEventCreate(&e));
-    for (int it = 0; it < 3; ++it) {
+    auto launch = [&](int it) {
         p.wp = weights[it % NL];
         hipLaunchKernelGGL((lsk_gemm_big_kernel<EPI, NTW, MT, PB, NW, PIN, KS, TR>), grid, dim3(NW * KS * 64), 0, 0, p);
-    }
+    };
+    for (int it = 0; it < 3; ++it) launch(it);
     CK(hipDeviceSynchronize());
     CK(hipEventRecord(a, 0));
-    for (int it = 0; it < g_iters; ++it) {
-        p.wp = weights[it % NL];
-        hipLaunchKernelGGL((lsk_gemm_big_kernel<EPI, NTW, MT, PB, NW, PIN, KS, TR>), grid, dim3(NW * KS * 64), 0, 0, p);
-    }
+    for (int it = 0; it < g_iters; ++it) launch(it);
     CK(hipEventRecord(e, 0));
     CK(hipEventSynchronize(e));
     float ms = 0.f;
@@ -84,8 +79,7 @@ static float run_cfg(const char* name, BigGemmParams p, const elem_t* const* wei
     const float us = ms * 1e3f / g_iters;
     // one clean run for the comparison: the residual epilogue accumulates into h, so h is restored first
     if (restore) CK(hipMemcpy(out, restore, out_elems * sizeof(elem_t), hipMemcpyDeviceToDevice));
-    p.wp = weights[0];
-    hipLaunchKernelGGL((lsk_gemm_big_kernel<EPI, NTW, MT, PB, NW, PIN, KS, TR>), grid, dim3(NW * KS * 64), 0, 0, p);
+    launch(0);
     CK(hipDeviceSynchronize());
     std::vector<unsigned short> host(out_elems);
     CK(hipMemcpy(host.data(), out, out_elems * sizeof(elem_t), hipMemcpyDeviceToHost));
@@ -108,11 +102,21 @@ static float run_cfg(const char* name, BigGemmParams p, const elem_t* const* wei
     return us;
 }
 
+// What the engine launches for a projection at a row count: the label of each value of the shape rules' enums (csrc/lsk_launch_big.h,
+// in the enums' order), the deepest ring of the instance and its K-split; the ring depth is launch_big's choice for this K.
+struct Pick { const char* shape; int pbmax, ks; };
+static const Pick QKV_PICKS[] = {{"64 x 128", 2, 1}, {"64 x 192", 2, 1}, {"128 x 192", 2, 1}, {"128 x 256 (8 waves)", 2, 1}, {"128 x 384 (8 waves), pinned", 2, 1}};
+static const Pick GATEUP_PICK = {"128 x 128, row-per-register", 2, 1};
+static const Pick RESID_PICKS[] = {{"32 x 128", 2, 2}, {"64 x 128, pinned", 2, 2}, {"128 x 128", 2, 2}, {"128 x 256 (8 waves), pinned", 2, 1}, {"128 x 128", 2, 1}, {"64 x 128, pinned", 4, 1}};
+static void print_pick(const Pick& k, int K) {
+    printf("  engine at this row count: %s, ring %d%s\n", k.shape, big_ring_depth(k.pbmax, K, k.ks), k.ks == 2 ? ", K-split 2" : "");
+}
+
 int main(int argc, char** argv) {
     std::vector<int> rows;
     for (int i = 1; i < argc; ++i) rows.push_back(atoi(argv[i]));
     if (rows.empty()) { rows.push_back(511); rows.push_back(2047); }
-    const int max_rows = 4096;
+    const int max_rows = MAX_ROWS;
     Bufs b;
     b.x = dalloc((size_t)max_rows * H); b.act_in = dalloc((size_t)max_rows * I); b.h = dalloc((size_t)max_rows * H);
     b.act_out = dalloc((size_t)max_rows * I); b.q = dalloc((size_t)max_rows * NH * HD);
@@ -125,7 +129,7 @@ int main(int argc, char** argv) {
     hipLaunchKernelGGL(fill_kernel, dim3(2048), dim3(256), 0, 0, h0, (size_t)max_rows * H, 13u, 1.0f);
     hipLaunchKernelGGL(fill_kernel, dim3(2048), dim3(256), 0, 0, b.cos, (size_t)(max_rows + 16) * HD / 2, 14u, 1.0f);
     hipLaunchKernelGGL(fill_kernel, dim3(2048), dim3(256), 0, 0, b.sin, (size_t)(max_rows + 16) * HD / 2, 15u, 1.0f);
-    CK(hipMalloc(&b.table, sizeof(int) * n_pages)); CK(hipMalloc(&b.kv_len, sizeof(int))); CK(hipMalloc(&b.sum, 8));
+    CK(hipMalloc(&b.table, sizeof(int) * n_pages)); CK(hipMalloc(&b.kv_len, sizeof(int)));
     std::vector<int> tab(n_pages);
     for (int i = 0; i < n_pages; ++i) tab[i] = i;
     CK(hipMemcpy(b.table, tab.data(), sizeof(int) * n_pages, hipMemcpyHostToDevice));
@@ -139,19 +143,17 @@ int main(int argc, char** argv) {
     for (int M : rows) {
         printf("== rows %d\n", M);
         {   // ---- q/k/v ----
-            BigGemmParams p{};
-            p.x = b.x; p.ldx = H; p.M = M; p.K = H; p.N = (NH + 2 * NKV) * HD; p.n_tiles = p.N / 16;
-            p.q_out = b.q; p.ldq = NH * HD; p.kpool = b.kpool; p.vpool = b.vpool; p.block_table = b.table; p.page_size = 128;
-            p.n_heads = NH; p.n_kv = NKV; p.head_dim = HD; p.rope_cos = b.cos; p.rope_sin = b.sin; p.kv_len = b.kv_len; p.pos_off = 0;
+            const BigGemmParams p = big_qkv(CFG, b.x, M, nullptr, b.cos, b.sin, b.kv_len, 0, b.table, b.q, b.kpool, b.vpool, LSK_WF_ELEM);   // (run_cfg sets wp)
             const double fl = 2.0 * M * (double)p.N * p.K;
             std::vector<unsigned short> first;
             printf(" q/k/v  (N = %d, K = %d)\n", p.N, p.K);
-            run_cfg<EPI_QKV, 2, 4, 2, 4, false, 1>("64 x 128, ring 2 (engine <= 1024 rows)", p, b.wqkv, b.q, (size_t)M * NH * HD, nullptr, b, &first, fl);
-            run_cfg<EPI_QKV, 2, 8, 2, 4, false, 1>("128 x 128, ring 2 (engine > 1024 rows)", p, b.wqkv, b.q, (size_t)M * NH * HD, nullptr, b, &first, fl);
+            print_pick(QKV_PICKS[big_qkv_shape(M, p.n_tiles)], p.K);
+            run_cfg<EPI_QKV, 2, 4, 2, 4, false, 1>("64 x 128, ring 2", p, b.wqkv, b.q, (size_t)M * NH * HD, nullptr, b, &first, fl);
+            run_cfg<EPI_QKV, 2, 8, 2, 4, false, 1>("128 x 128, ring 2", p, b.wqkv, b.q, (size_t)M * NH * HD, nullptr, b, &first, fl);
             run_cfg<EPI_QKV, 2, 4, 4, 4, false, 1>("64 x 128, ring 4", p, b.wqkv, b.q, (size_t)M * NH * HD, nullptr, b, &first, fl);
             run_cfg<EPI_QKV, 2, 4, 2, 8, false, 1>("64 x 256 (8 waves), ring 2", p, b.wqkv, b.q, (size_t)M * NH * HD, nullptr, b, &first, fl);
             run_cfg<EPI_QKV, 2, 4, 2, 4, false, 2>("64 x 128, ring 2, K-split 2", p, b.wqkv, b.q, (size_t)M * NH * HD, nullptr, b, &first, fl);
-            if (getenv("LSK_BENCH_EXPLORE")) {      // tile shapes that are not in the engine (three 16-column tiles per wave: 192-column workgroup tiles)
+            if (getenv("LSK_BENCH_EXPLORE")) {      // every other tile shape that compiles
                 run_cfg<EPI_QKV, 3, 8, 2, 4, false, 1>("128 x 192, ring 2", p, b.wqkv, b.q, (size_t)M * NH * HD, nullptr, b, &first, fl);
                 run_cfg<EPI_QKV, 3, 8, 2, 4, false, 2>("128 x 192, ring 2, K-split 2", p, b.wqkv, b.q, (size_t)M * NH * HD, nullptr, b, &first, fl);
                 run_cfg<EPI_QKV, 3, 4, 2, 4, false, 1>("64 x 192, ring 2", p, b.wqkv, b.q, (size_t)M * NH * HD, nullptr, b, &first, fl);
@@ -169,12 +171,12 @@ int main(int argc, char** argv) {
             }
         }
         {   // ---- gate/up ----
-            BigGemmParams p{};
-            p.x = b.x; p.ldx = H; p.M = M; p.K = H; p.N = 2 * I; p.n_tiles = p.N / 16; p.act = b.act_out; p.ldact = I;
+            const BigGemmParams p = big_swiglu(CFG, b.x, M, nullptr, b.act_out, LSK_WF_ELEM);
             const double fl = 2.0 * M * (double)p.N * p.K;
             std::vector<unsigned short> first;
             printf(" gate/up (N = %d, K = %d)\n", p.N, p.K);
-            run_cfg<EPI_SWIGLU, 2, 8, 2, 4, false, 1, false>("128 x 128, ring 2, row-per-register (engine)", p, b.wgu, b.act_out, (size_t)M * I, nullptr, b, &first, fl);
+            print_pick(GATEUP_PICK, p.K);
+            run_cfg<EPI_SWIGLU, 2, 8, 2, 4, false, 1, false>("128 x 128, ring 2, row-per-register", p, b.wgu, b.act_out, (size_t)M * I, nullptr, b, &first, fl);
             run_cfg<EPI_SWIGLU, 2, 8, 2, 4, false, 1, true>("128 x 128, ring 2, transposed", p, b.wgu, b.act_out, (size_t)M * I, nullptr, b, &first, fl);
             run_cfg<EPI_SWIGLU, 2, 8, 2, 4, false, 2, false>("128 x 128, ring 2, K-split 2", p, b.wgu, b.act_out, (size_t)M * I, nullptr, b, &first, fl);
             if (getenv("LSK_BENCH_EXPLORE")) {
@@ -188,15 +190,14 @@ int main(int argc, char** argv) {
             }
         }
         for (int which = 0; which < 2; ++which) {   // ---- o_proj, down ----
-            BigGemmParams p{};
-            const int K = which ? I : NH * HD;
-            p.x = which ? b.act_in : b.x; p.ldx = K; p.M = M; p.K = K; p.N = H; p.n_tiles = p.N / 16; p.h = b.h; p.ldh = H;
+            const BigGemmParams p = big_resid(which ? b.act_in : b.x, M, which ? I : NH * HD, nullptr, H, b.h, LSK_WF_ELEM);
             const double fl = 2.0 * M * (double)p.N * p.K;
             std::vector<unsigned short> first;
             printf(" %s (N = %d, K = %d)\n", which ? "down" : "o_proj", p.N, p.K);
-            run_cfg<EPI_RESID, 2, 4, 4, 4, true, 1>("64 x 128, ring 4, pinned (engine, > 384 wgs)", p, which ? b.wdown : b.wo, b.h, (size_t)M * H, h0, b, &first, fl);
-            run_cfg<EPI_RESID, 2, 4, 2, 4, true, 2>("64 x 128, ring 2, pinned, K-split 2 (engine, <= 384 wgs)", p, which ? b.wdown : b.wo, b.h, (size_t)M * H, h0, b, &first, fl);
-            run_cfg<EPI_RESID, 2, 8, 2, 4, false, 1>("128 x 128, ring 2 (engine, >= 512 wgs of 128 rows)", p, which ? b.wdown : b.wo, b.h, (size_t)M * H, h0, b, &first, fl);
+            print_pick(RESID_PICKS[big_resid_shape(M, p.n_tiles, p.K)], p.K);
+            run_cfg<EPI_RESID, 2, 4, 4, 4, true, 1>("64 x 128, ring 4, pinned", p, which ? b.wdown : b.wo, b.h, (size_t)M * H, h0, b, &first, fl);
+            run_cfg<EPI_RESID, 2, 4, 2, 4, true, 2>("64 x 128, ring 2, pinned, K-split 2", p, which ? b.wdown : b.wo, b.h, (size_t)M * H, h0, b, &first, fl);
+            run_cfg<EPI_RESID, 2, 8, 2, 4, false, 1>("128 x 128, ring 2", p, which ? b.wdown : b.wo, b.h, (size_t)M * H, h0, b, &first, fl);
             run_cfg<EPI_RESID, 2, 4, 4, 4, true, 2>("64 x 128, ring 4, pinned, K-split 2", p, which ? b.wdown : b.wo, b.h, (size_t)M * H, h0, b, &first, fl);
             run_cfg<EPI_RESID, 2, 8, 2, 4, false, 2>("128 x 128, ring 2, K-split 2", p, which ? b.wdown : b.wo, b.h, (size_t)M * H, h0, b, &first, fl);
             run_cfg<EPI_RESID, 2, 2, 2, 4, false, 2>("32 x 128, ring 2, K-split 2", p, which ? b.wdown : b.wo, b.h, (size_t)M * H, h0, b, &first, fl);
