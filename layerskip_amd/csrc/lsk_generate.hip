@@ -5,7 +5,7 @@
 
 #include "lsk_engine.h"
 #include "lsk_accept.h"
-#include "lsk_sample.h"      // needs the LSK_RES_* result-block layout of lsk_accept.h
+#include "lsk_sample.h"      // the sampling kernels and their launchers; needs the LSK_RES_* result-block layout of lsk_accept.h
 
 // Upload what a step needs from the host (the prompt rows / a changed input token / a changed eos list).
 static int upload_step_inputs(lsk_engine* e, const int32_t* input_ids, int P, const int32_t* eos_token_ids, int n_eos, hipStream_t st) {
@@ -39,60 +39,6 @@ struct StepSampling {
     int ld;
 };
 
-// The large-vocabulary draw is a SEQUENCE of launches that hand histograms, row maxima and row states to each other and leave them zero
-// for the next draw (the last kernel of the sequence clears what the others filled).  If a launch of the sequence fails, the ones
-// behind it never run and the state stays dirty -- every later draw would silently use wrong masses.  So a failed sequence zeroes
-// the whole state before the error is returned.
-static int sample_sequence_status(lsk_engine* e, hipStream_t st) {
-    const hipError_t err = hipGetLastError();
-    if (err == hipSuccess) return 0;
-    if (e->samp_hist != nullptr && e->samp_state_bytes) (void)hipMemsetAsync(e->samp_hist, 0, e->samp_state_bytes, st);
-    return lsk_fail("sample=True: a launch of the draw sequence failed: %s (sampling state cleared)", hipGetErrorString(err));
-}
-
-// m rows of sm.logits drawn at Philox counter sm.offset with tags tag0, tag0 + 1, ...: tokens -> tokens_dev, warped distributions -> probs
-static int launch_sample(lsk_engine* e, const StepSampling& sm, int m, int tag0, int* tokens_dev, float* probs, elem_t* embed_dst, hipStream_t st) {
-    // (lsk_engine_set_globals accepts a NULL embedding -- a pipeline rank that embeds nothing; a draw that is to leave its token's embedding
-    // row behind needs one)
-    if (embed_dst != nullptr && !e->embed) return lsk_fail("sample=True: the embedding is not bound on this engine (only rank 0 of a pipeline drafts)");
-    SampleParams sp{};
-    sp.logits = sm.logits; sp.ld = sm.ld; sp.vocab = e->cfg.vocab; sp.inv_temperature = 1.0f / sm.temperature;
-    sp.top_k = sm.top_k; sp.top_p = sm.top_p;
-    sp.seed_lo = (unsigned int)sm.seed; sp.seed_hi = (unsigned int)(sm.seed >> 32);
-    sp.off_lo = (unsigned int)sm.offset; sp.off_hi = (unsigned int)(sm.offset >> 32);
-    sp.tag0 = tag0; sp.tokens_out = tokens_dev; sp.probs_out = probs;
-    sp.embed = e->embed; sp.hidden = e->cfg.hidden; sp.embed_dst = embed_dst;
-    if (sp.vocab <= LSK_SAMPLE_REG_VOCAB || e->samp_hist == nullptr || (sm.ld & 3)) {
-        hipLaunchKernelGGL(lsk_sample_kernel, dim3(m), dim3(LSK_SAMPLE_THREADS), 0, st, sp);
-        HIP_OK(hipGetLastError());
-        return 0;
-    }
-    // large vocabularies: the row spread over ns workgroups, masses in a full-resolution histogram (lsk_sample.h)
-    SampleBigParams bp{};
-    bp.s = sp; bp.hist = e->samp_hist; bp.cnt = e->samp_cnt; bp.rows = (SampleRowState*)e->samp_rows;
-    bp.part_val = e->samp_part_val; bp.part_idx = e->samp_part_idx;
-    const int groups = (sp.vocab + 3) / 4;
-    bp.ns = (groups + LSK_SAMPLE_THREADS - 1) / LSK_SAMPLE_THREADS;
-    if (bp.ns > 64) bp.ns = 64;
-    if (m > LSK_MAX_ROWS + 1) return lsk_fail("launch_sample: %d rows", m);
-    const dim3 wide(bp.ns, m), one(1, m);
-    hipLaunchKernelGGL(lsk_sample_max_kernel, wide, dim3(LSK_SAMPLE_THREADS), 0, st, bp);
-    if (!(sp.top_k > 0 && sp.top_k < sp.vocab)) {               // no top-k (the default): the two-level form
-        SampleTwoLevelParams tp{};
-        tp.b = bp; tp.coarse = e->samp_coarse; tp.fine = e->samp_coarse + (size_t)(LSK_MAX_ROWS + 1) * 256;
-        hipLaunchKernelGGL(lsk_sample_coarse_kernel, wide, dim3(LSK_SAMPLE_THREADS), 0, st, tp);
-        hipLaunchKernelGGL(lsk_sample_fine_kernel, wide, dim3(LSK_SAMPLE_THREADS), 0, st, tp);
-        hipLaunchKernelGGL(lsk_sample_draw2_kernel, wide, dim3(LSK_SAMPLE_THREADS), 0, st, tp);
-        hipLaunchKernelGGL(lsk_sample_pick2_kernel, dim3(m), dim3(256), 0, st, tp);
-        return sample_sequence_status(e, st);
-    }
-    hipLaunchKernelGGL(lsk_sample_hist_kernel, wide, dim3(LSK_SAMPLE_THREADS), 0, st, bp);
-    hipLaunchKernelGGL(lsk_sample_scan_kernel, one, dim3(LSK_SAMPLE_THREADS), 0, st, bp);
-    hipLaunchKernelGGL(lsk_sample_draw_kernel, wide, dim3(LSK_SAMPLE_THREADS), 0, st, bp);
-    hipLaunchKernelGGL(lsk_sample_pick_kernel, dim3(m), dim3(256), 0, st, bp);
-    return sample_sequence_status(e, st);
-}
-
 // Final norm + lm_head over m rows of x, then each row's token into tokens_dev[0..m).  sm == nullptr: the argmax; embed_dst receives the
 // token's embedding row and kv_add > 0 advances the context in the same launch.  Otherwise the head writes logits only (the token is
 // drawn, not maximised) and launch_sample draws with tags tag0.. at sm->offset, leaving the warped distributions in `probs`; a head
@@ -101,7 +47,11 @@ static int head_token(lsk_engine* e, const elem_t* x, int m, int* tokens_dev, el
                       const StepSampling* sm, int tag0, float* probs) {
     if (sm == nullptr) return lsk_run_head_dev(e, x, m, nullptr, 0, tokens_dev, st, embed_dst, kv_add);
     LSK_TRY(lsk_run_head_dev(e, x, m, sm->logits, sm->ld, nullptr, st, nullptr, kv_add));
-    return launch_sample(e, *sm, m, tag0, tokens_dev, probs, embed_dst, st);
+    // (lsk_engine_set_globals accepts a NULL embedding -- a pipeline rank that embeds nothing; a draw that is to leave its token's embedding
+    // row behind needs one)
+    if (embed_dst != nullptr && !e->embed) return lsk_fail("sample=True: the embedding is not bound on this engine (only rank 0 of a pipeline drafts)");
+    return launch_sample(e, sm->logits, sm->ld, e->cfg.vocab, m, sm->temperature, sm->top_k, sm->top_p, sm->seed, sm->offset, tag0, tokens_dev, probs,
+                         e->embed, e->cfg.hidden, embed_dst, st);
 }
 
 // The prompt from host ids: all rows but the last through layers [0, layer_end), the last id's embedding into hrow[0].
@@ -365,7 +315,7 @@ extern "C" int lsk_spec_generate(lsk_engine* e, const int32_t* prompt_ids, int32
 // DRAW CONTRACT.  In a sampled autoregressive generation with key `seed` and counter base `offset`, token i is the draw
 // lsk_sample_rows makes over that position's logits row at counter `offset + i` with tag0 = LSK_TAG_VERIFY (row 0 of the
 // draw).  That is exactly the draw step i of lsk_spec_generate_sampled makes with num_speculations = 0: nothing is drafted,
-// the verify block is the one input row at full depth, launch_sample(..., 1 row, LSK_TAG_VERIFY) at offset + i, and the
+// the verify block is the one input row at full depth, launch_sample (lsk_sample.h) of 1 row with LSK_TAG_VERIFY at offset + i, and the
 // acceptance kernel emits that token unchanged.  So under one (seed, offset) the fused loop, the stepwise form and the layer
 // pipeline's zero-speculation sampled step (lsk_pipeline_tail_sampled) give the same tokens.
 //
@@ -507,8 +457,9 @@ static int pipeline_pack_impl(lsk_engine* e, int go, int prompt_len, int src_row
     LSK_TRY(lsk_ready(e));
     if (m < 1 || src_row < 0 || src_row + m > LSK_MAX_ROWS) return lsk_fail("lsk_pipeline_pack: rows [%d,%d) exceed the step buffer", src_row, src_row + m);
     if (prompt_len < 0 || kv < 0 || kv > e->cfg.max_ctx) return lsk_fail("lsk_pipeline_pack: bad header values");
+    const LskPhilox rng = lsk_philox_of(0, offset);
     hipLaunchKernelGGL(lsk_pipeline_pack_kernel, dim3(1 + (go ? m : 0)), dim3(256), 0, st, e->hrow, e->row_tokens, src_row, m, e->cfg.hidden,
-                       go ? 1 : 0, prompt_len, kv, e->hmsg, p_draft, ld, (unsigned int)offset, (unsigned int)(offset >> 32));
+                       go ? 1 : 0, prompt_len, kv, e->hmsg, p_draft, ld, rng.off_lo, rng.off_hi);
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -535,12 +486,7 @@ static int pipeline_tail_impl(lsk_engine* e, int m, int* result, hipStream_t st,
     if (sm == nullptr) {
         hipLaunchKernelGGL(lsk_pipeline_accept_kernel, dim3(1), dim3(64), 0, st, e->hmsg, e->verified, e->eos, e->n_eos_host, e->state, result);
     } else {
-        PipeAcceptSampledParams ap{};
-        ap.msg = e->hmsg; ap.verified = e->verified; ap.eos = e->eos; ap.n_eos = e->n_eos_host; ap.p_verify = sm->p_verify; ap.ld = sm->ld;
-        ap.seed_lo = (unsigned int)sm->seed; ap.seed_hi = (unsigned int)(sm->seed >> 32);
-        ap.off_lo = (unsigned int)sm->offset; ap.off_hi = (unsigned int)(sm->offset >> 32);
-        ap.tag_accept = LSK_TAG_ACCEPT; ap.st = e->state; ap.result = result;
-        hipLaunchKernelGGL(lsk_pipeline_accept_sampled_kernel, dim3(1), dim3(LSK_SAMPLE_THREADS), 0, st, ap);
+        launch_pipeline_accept_sampled(e->hmsg, e->verified, e->eos, e->n_eos_host, sm->p_verify, sm->ld, sm->seed, sm->offset, e->state, result, st);
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -595,10 +541,8 @@ extern "C" int lsk_sample_rows(lsk_engine* e, const void* logits, int32_t ld, in
     if (!logits || !tokens_out || !probs_out) return lsk_fail("lsk_sample_rows: null pointer");
     if (m < 1 || m > LSK_MAX_ROWS + 1 || ld < e->cfg.vocab) return lsk_fail("lsk_sample_rows: m=%d ld=%d out of range", m, ld);
     LSK_TRY(check_sampling_args(temperature, &top_p));
-    StepSampling sm{};
-    sm.temperature = temperature; sm.top_k = top_k; sm.top_p = top_p; sm.seed = seed; sm.offset = offset;
-    sm.logits = (float*)logits; sm.ld = ld;
-    return launch_sample(e, sm, m, tag0, tokens_out, (float*)probs_out, nullptr, (hipStream_t)stream);
+    return launch_sample(e, (const float*)logits, ld, e->cfg.vocab, m, temperature, top_k, top_p, seed, offset, tag0, tokens_out, (float*)probs_out,
+                         e->embed, e->cfg.hidden, nullptr, (hipStream_t)stream);
 }
 
 static int make_step_sampling(lsk_engine* e, float temperature, int32_t top_k, float top_p, uint64_t seed, uint64_t offset, void* scratch,
@@ -694,9 +638,8 @@ extern "C" int lsk_pipeline_residual(lsk_engine* e, void* result_dev, int32_t re
     StepSampling sm;
     LSK_TRY(make_step_sampling(e, 1.0f, 0, 1.0f, seed, offset, scratch, scratch_bytes, &sm));
     if (result_words < LSK_PRES_QROW + sm.ld) return lsk_fail("lsk_pipeline_residual: result block of %d words, %d needed", result_words, LSK_PRES_QROW + sm.ld);
-    hipLaunchKernelGGL(lsk_pipeline_residual_kernel, dim3(1), dim3(LSK_SAMPLE_THREADS), 0, (hipStream_t)stream, (int*)result_dev,
-                       sm.p_draft + (size_t)src_row * sm.ld, sm.ld, e->cfg.vocab, e->row_tokens + src_row + 1, (unsigned int)seed,
-                       (unsigned int)(seed >> 32), (unsigned int)offset, (unsigned int)(offset >> 32), LSK_TAG_RESIDUAL);
+    launch_pipeline_residual((int*)result_dev, sm.p_draft + (size_t)src_row * sm.ld, sm.ld, e->cfg.vocab, e->row_tokens + src_row + 1, seed, offset,
+                             (hipStream_t)stream);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -1,9 +1,9 @@
 // Sampling side of the speculation step on the device: what the reference does on the host with
 // torch ops per token -- `logits / temperature` -> top-k -> top-p -> softmax -> multinomial (decode_next_token,
 // llama_model_utils.py:109-131) and the modified rejection sampling of single_step_speculation
-// (self_speculation_generator.py:191-199, max_fn :27-29) -- as two kernels over logits that never leave HBM.
+// (self_speculation_generator.py:191-199, max_fn :27-29) -- as kernels over logits that never leave HBM.
 //
-//   lsk_sample_kernel: one 1024-thread workgroup per logits row (V <= 128256 floats, L2 resident).
+//   lsk_sample_kernel: one 1024-thread workgroup per logits row.
 //     * the logits are bf16-exact fp32 values, so a row lives in a 16-bit ORDERED KEY space (sign-folded upper half of
 //       the fp32 pattern).  Both filters are thresholds in that space, found by a 16-step bisection whose predicate
 //       is one block reduction:
@@ -16,16 +16,32 @@
 //       softmax(z), with no ordered prefix sum and no dependence on the thread layout;
 //     * the normalised probabilities of the warped distribution are written out: the rejection step needs the
 //       draft's and the verifier's full rows.
+//   lsk_sample_{max,hist,scan,draw,pick} / {max,coarse,fine,draw2,pick2}: the same draw of a llama3-sized row spread over
+//     `ns` workgroups, the thresholds read off integer mass histograms instead of searched.
 //   lsk_accept_sampled_kernel: one workgroup.  Draft i is kept while u_i < min(1, q_i(x_i) / p_i(x_i)); at the first
 //     rejection the emitted token is a Gumbel-max draw from max(q - p, 0) (normalisation-free, so max_fn's 1e-6
 //     regulariser has nothing to regularise); if all drafts are kept it is the token sampled from the last verify
 //     row.  Then the same bookkeeping as the greedy lsk_accept_kernel: result block, kv_len rollback, next input token.
+//
+// Every form makes the same draw from the same Philox counters because each STAGE is written once and the forms only differ in
+// where a row's elements and thresholds come from:
+//   lsk_load_quad / lsk_store_quad   four consecutive elements with a ragged tail (one 16-byte access where the row is aligned)
+//   lsk_quad_terms                   (z, exp z, kept?) of a quad read from memory
+//   lsk_draw_quad                    Philox -> probabilities stored -> Gumbel scores -> running best: the per-quad step of EVERY draw
+//   lsk_sample_row_cached / _reread  max -> top-k search -> Z -> top-p search -> Z_kept over the row in registers / re-read from memory
+//                                    (the one stage still written per form: see there), then the shared draw and token tail
+//   lsk_sample_draw_part             a workgroup's share of a spread row's draw and its winner (both multi-workgroup forms)
+//   lsk_sample_pick_row              the winner among the partials;  lsk_sample_emit: clamp, token store, row 0's embedding gather
+//   lsk_accept_test                  u_i < min(1, q / p) over the counted drafts (one GPU and the layer pipeline's last rank)
+//   lsk_residual_draw                the draw from max(q - p, 0) (one GPU and the pipeline's rank 0)
+// and the host side (bottom of the file) builds each launch once, for the engine and the test library.
 // Parity is "in distribution" (the reference draws from torch's generator in a different order); the oracle
 // (oracle/sampling_oracle.py) restates THIS algorithm with the same Philox stream so that kernel and oracle can be
 // compared draw for draw, and restates the reference's warping so that the kept sets can be compared with HF's.
 #pragma once
 #include "lsk_common.h"
 #include "lsk_accept.h"      // result-block layout (LSK_RES_*), the header words, lsk_drafts_until_eos
+#include "lsk_engine.h"      // the samp_* workspace of the large-vocabulary launches
 
 #define LSK_SAMPLE_THREADS 1024
 #define LSK_SAMPLE_WAVES 16
@@ -36,6 +52,12 @@
 #define LSK_TAG_ACCEPT 64
 #define LSK_TAG_RESIDUAL 96
 
+// Philox key (seed) and counter words 2-3 (offset) of one step; every parameter block carries one
+struct LskPhilox { unsigned int seed_lo, seed_hi, off_lo, off_hi; };
+static inline LskPhilox lsk_philox_of(uint64_t seed, uint64_t offset) {
+    return {(unsigned int)seed, (unsigned int)(seed >> 32), (unsigned int)offset, (unsigned int)(offset >> 32)};
+}
+
 struct SampleParams {
     const float* logits;        // [m][ld] fp32 (bf16-exact values), device
     int ld;
@@ -43,8 +65,7 @@ struct SampleParams {
     float inv_temperature;
     int top_k;                  // <= 0 or >= vocab: disabled
     float top_p;                // >= 1: disabled
-    unsigned int seed_lo, seed_hi;
-    unsigned int off_lo, off_hi;
+    LskPhilox rng;
     int tag0;                   // RNG row tag of row 0 (row r uses tag0 + r)
     int* tokens_out;            // [m]
     float* probs_out;           // [m][ld]
@@ -93,6 +114,18 @@ __host__ __device__ inline int lsk_key16(float x) {
 
 __device__ __forceinline__ float lsk_gumbel(unsigned int bits) { return -__logf(-__logf(lsk_u01(bits))); }
 
+// the four words of counter (c0, tag, offset) under the step's key
+__device__ __forceinline__ void lsk_philox_words(const LskPhilox& r, int c0, int tag, unsigned int (&out)[4]) {
+    lsk_philox4x32_10((unsigned int)c0, (unsigned int)tag, r.off_lo, r.off_hi, r.seed_lo, r.seed_hi, out);
+}
+
+// the best Gumbel score so far and its element; the lowest index wins ties.  A NaN row leaves no score above -inf and the index stays
+// 0x7fffffff, which lsk_sample_emit clamps.
+struct SampleBest { float val = -INFINITY; int idx = 0x7fffffff; };
+__device__ __forceinline__ void lsk_best_update(SampleBest& b, float v, int idx) {
+    if (v > b.val || (v == b.val && idx < b.idx)) { b.val = v; b.idx = idx; }
+}
+
 // ---- block reductions over 1024 threads (DPP inside a wave, LDS across the 16 waves) ----
 __device__ __forceinline__ float wave_max(float v) {
     const int r = __builtin_bit_cast(int, row16_max(v));
@@ -127,29 +160,87 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     return s;
 }
 
-// argmax with the lowest index winning ties; every thread gets the winner
-__device__ __forceinline__ int block_argmax(float v, int idx, float* red, int* redi) {
+// the workgroup's best (lowest index on ties); every thread gets it
+__device__ __forceinline__ SampleBest block_argmax(SampleBest b, float* red, int* redi) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o, 64);
-        const int oi = __shfl_xor(idx, o, 64);
-        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-    }
+    for (int o = 32; o > 0; o >>= 1) lsk_best_update(b, __shfl_xor(b.val, o, 64), __shfl_xor(b.idx, o, 64));
     const int w = threadIdx.x >> 6;
     __syncthreads();
-    if ((threadIdx.x & 63) == 0) { red[w] = v; redi[w] = idx; }
+    if ((threadIdx.x & 63) == 0) { red[w] = b.val; redi[w] = b.idx; }
     __syncthreads();
-    float bv = red[0];
-    int bi = redi[0];
+    b = SampleBest{red[0], redi[0]};
 #pragma unroll
-    for (int i = 1; i < LSK_SAMPLE_WAVES; ++i) {
-        const float ov = red[i];
-        const int oi = redi[i];
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    return bi;
+    for (int i = 1; i < LSK_SAMPLE_WAVES; ++i) lsk_best_update(b, red[i], redi[i]);
+    return b;
 }
 
+// ---- the stages of a draw, each written once ------------------------------------------------------------------------------------
+// Elements 4 gq .. 4 gq + 3 of a row of V (`fill` where there is none).  aligned: the row starts on a 16-byte boundary (ld is a
+// multiple of 4 floats), so a whole quad is one access.
+__device__ __forceinline__ float4 lsk_load_quad(const float* x, int gq, int V, float fill, bool aligned = true) {
+    float4 v = {fill, fill, fill, fill};
+    const int i0 = 4 * gq;
+    if (aligned && i0 + 3 < V) v = *(const float4*)(x + i0);
+    else {
+        if (i0 < V) v.x = x[i0];
+        if (i0 + 1 < V) v.y = x[i0 + 1];
+        if (i0 + 2 < V) v.z = x[i0 + 2];
+        if (i0 + 3 < V) v.w = x[i0 + 3];
+    }
+    return v;
+}
+__device__ __forceinline__ void lsk_store_quad(float* y, int gq, int V, const float (&v)[4], bool aligned) {
+    if (aligned && 4 * gq + 3 < V) *(float4*)(y + 4 * gq) = float4{v[0], v[1], v[2], v[3]};
+    else
+        for (int j = 0; j < 4; ++j)
+            if (4 * gq + j < V) y[4 * gq + j] = v[j];
+}
+
+// What the draw needs of a quad: z = (x - max) / temperature, exp z, and whether the element survives both filters (key >= P)
+struct SampleQuad { float z[4], e[4]; bool keep[4]; };
+__device__ __forceinline__ SampleQuad lsk_quad_terms(const float4 v, int gq, int V, int P, float m, float it) {
+    const float xs[4] = {v.x, v.y, v.z, v.w};
+    SampleQuad q;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        q.keep[j] = 4 * gq + j < V && lsk_key16(xs[j]) >= P;
+        q.z[j] = (xs[j] - m) * it;
+        q.e[j] = __expf(q.z[j]);
+    }
+    return q;
+}
+
+// The per-quad step of every draw: the quad's Philox words, its normalised probabilities stored, its Gumbel scores into `best`
+__device__ __forceinline__ void lsk_draw_quad(const SampleParams& p, int row, int gq, const SampleQuad& q, float inv_z, bool aligned, SampleBest& best) {
+    unsigned int rnd[4];
+    lsk_philox_words(p.rng, gq, p.tag0 + row, rnd);
+    float pr[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        pr[j] = q.keep[j] ? q.e[j] * inv_z : 0.f;
+        lsk_best_update(best, q.keep[j] ? q.z[j] + lsk_gumbel(rnd[j]) : -INFINITY, 4 * gq + j);
+    }
+    lsk_store_quad(p.probs_out + (size_t)row * p.ld, gq, p.vocab, pr, aligned);
+}
+
+// The token tail of a draw (THREADS threads, `winner` the same in all): clamped like the greedy finalize kernel does, so that neither
+// the stored token nor the embedding gather can leave the vocabulary; row 0's embedding row into the next input row
+template <int THREADS>
+__device__ __forceinline__ void lsk_sample_emit(const SampleParams& p, int row, int winner) {
+    const int tok = min(max(winner, 0), p.vocab - 1);
+    if (threadIdx.x == 0) p.tokens_out[row] = tok;
+    if (row == 0 && p.embed_dst != nullptr) {
+        const elem8* src = (const elem8*)(p.embed + (size_t)tok * p.hidden);
+        elem8* dst = (elem8*)p.embed_dst;
+        for (int i = threadIdx.x; i < p.hidden / 8; i += THREADS) dst[i] = src[i];
+    }
+}
+
+// ---- one workgroup per row: the thresholds by bisection, each predicate one block reduction ------------------------------------------
+// Two forms, which differ in where a thread's elements live and in which order it adds them up (so each keeps its sums bit for bit);
+// load, per-quad draw step and token tail are the shared ones above.  The SEARCH is written out in both: written once over a row
+// accessor it cost the register form its occupancy (128 VGPRs and 48 bytes of scratch instead of 124 and none).
+//
 // The row held in REGISTERS (V <= 32 768: the llama2 vocabularies): thread t owns the 8 quads 4 (t + 1024 k) .. + 3, k < 8 -- the
 // same quads its Philox counters cover in the draw.  Every logit is read from memory once and its exponential computed once; the
 // ~35 bisection steps of the two filters are then compares and adds on registers plus one block reduction each (they were ~35
@@ -165,14 +256,7 @@ __device__ __forceinline__ void lsk_sample_row_cached(const SampleParams& p, con
     float m = -INFINITY;
 #pragma unroll
     for (int k = 0; k < LSK_SAMPLE_QUADS; ++k) {
-        const int i0 = 4 * (tid + LSK_SAMPLE_THREADS * k);
-        float4 v = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        if (i0 + 3 < V) v = *(const float4*)(x + i0);          // rows start 16-byte aligned (ld is a multiple of 4 floats)
-        else {
-            if (i0 < V) v.x = x[i0];
-            if (i0 + 1 < V) v.y = x[i0 + 1];
-            if (i0 + 2 < V) v.z = x[i0 + 2];
-        }
+        const float4 v = lsk_load_quad(x, tid + LSK_SAMPLE_THREADS * k, V, -INFINITY);
         xv[k][0] = v.x; xv[k][1] = v.y; xv[k][2] = v.z; xv[k][3] = v.w;
 #pragma unroll
         for (int j = 0; j < 4; ++j) m = fmaxf(m, xv[k][j]);
@@ -236,60 +320,39 @@ __device__ __forceinline__ void lsk_sample_row_cached(const SampleParams& p, con
         for (int j = 0; j < 4; ++j) z += (key[k][j] >= P) ? ev[k][j] : 0.f;
     z = block_sum(z, red);
     const float inv_z = 1.0f / z;
-    float best = -INFINITY;
-    int best_i = 0x7fffffff;
-    float* po = p.probs_out + (size_t)row * p.ld;
+    SampleBest best;
 #pragma unroll
     for (int k = 0; k < LSK_SAMPLE_QUADS; ++k) {
         const int gq = tid + LSK_SAMPLE_THREADS * k;
-        if (4 * gq < V) {
-            unsigned int rnd[4];
-            lsk_philox4x32_10((unsigned int)gq, (unsigned int)(p.tag0 + row), p.off_lo, p.off_hi, p.seed_lo, p.seed_hi, rnd);
-            float pr[4];
+        if (4 * gq >= V) continue;
+        SampleQuad q;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int i = gq * 4 + j;
-                const bool keep = key[k][j] >= P;                // (-1 for i >= V: never kept)
-                pr[j] = keep ? ev[k][j] * inv_z : 0.f;
-                const float s = keep ? (xv[k][j] - m) * it + lsk_gumbel(rnd[j]) : -INFINITY;
-                if (s > best || (s == best && i < best_i)) { best = s; best_i = i; }
-            }
-            if (4 * gq + 3 < V) *(float4*)(po + 4 * gq) = float4{pr[0], pr[1], pr[2], pr[3]};
-            else
-                for (int j = 0; j < 4; ++j)
-                    if (4 * gq + j < V) po[4 * gq + j] = pr[j];
-        }
+        for (int j = 0; j < 4; ++j) { q.keep[j] = key[k][j] >= P; q.z[j] = (xv[k][j] - m) * it; q.e[j] = ev[k][j]; }
+        lsk_draw_quad(p, row, gq, q, inv_z, true, best);            // with the cached exponential
     }
-    // a NaN row leaves no score above -inf (best_i stays 0x7fffffff): clamp like the greedy finalize kernel does, so that neither the
-    // stored token nor the embedding gather below can leave the vocabulary
-    const int tok = min(max(block_argmax(best, best_i, red, redi), 0), p.vocab - 1);
-    if (tid == 0) p.tokens_out[row] = tok;
-    if (row == 0 && p.embed_dst != nullptr) {
-        const elem8* src = (const elem8*)(p.embed + (size_t)tok * p.hidden);
-        elem8* dst = (elem8*)p.embed_dst;
-        for (int i = tid; i < p.hidden / 8; i += LSK_SAMPLE_THREADS) dst[i] = src[i];
-    }
+    lsk_sample_emit<LSK_SAMPLE_THREADS>(p, row, block_argmax(best, red, redi).idx);
 }
 
-__global__ __launch_bounds__(LSK_SAMPLE_THREADS) void lsk_sample_kernel(const SampleParams p) {
-    __shared__ float red[LSK_SAMPLE_WAVES];
-    __shared__ int redi[LSK_SAMPLE_WAVES];
-    const int row = blockIdx.x;
-    static_assert(4 * LSK_SAMPLE_QUADS * LSK_SAMPLE_THREADS == LSK_SAMPLE_REG_VOCAB, "register path capacity");
-    if (p.vocab <= LSK_SAMPLE_REG_VOCAB && (p.ld & 3) == 0) {
-        lsk_sample_row_cached(p, row, red, redi);
-        return;
-    }
+// The row RE-READ from memory in every pass (a caller-owned buffer whose ld is no multiple of 4, at either vocabulary size): thread t owns
+// elements t + 1024 k in the sums and quads t + 1024 k in the draw; rows need not be 16-byte aligned, so every access is a scalar one.
+__device__ __forceinline__ void lsk_sample_row_reread(const SampleParams& p, const int row, float* red, int* redi) {
     const int tid = threadIdx.x;
     const int V = p.vocab;
     const float* x = p.logits + (size_t)row * p.ld;
     const float it = p.inv_temperature;
-
     float m = -INFINITY;
     for (int i = tid; i < V; i += LSK_SAMPLE_THREADS) m = fmaxf(m, x[i]);
     m = block_max(m, red);
     const int key_max = lsk_key16(m);
-
+    // the thread's share of sum{exp z : key >= T}
+    auto mass_from = [&](int T) {
+        float z = 0.f;
+        for (int i = tid; i < V; i += LSK_SAMPLE_THREADS) {
+            const float xi = x[i];
+            if (lsk_key16(xi) >= T) z += __expf((xi - m) * it);
+        }
+        return z;
+    };
     // ---- top-k: largest key K with count{key >= K} >= k ----
     int K = 0;
     if (p.top_k > 0 && p.top_k < V) {
@@ -298,72 +361,36 @@ __global__ __launch_bounds__(LSK_SAMPLE_THREADS) void lsk_sample_kernel(const Sa
             const int mid = (lo + hi + 1) >> 1;
             float c = 0.f;                                 // counts <= 128256 are exact in fp32
             for (int i = tid; i < V; i += LSK_SAMPLE_THREADS) c += (lsk_key16(x[i]) >= mid) ? 1.f : 0.f;
-            c = block_sum(c, red);
-            if (c >= (float)p.top_k) lo = mid; else hi = mid - 1;
+            if (block_sum(c, red) >= (float)p.top_k) lo = mid; else hi = mid - 1;
         }
         K = lo;
     }
     // ---- top-p on the top-k survivors: smallest key P >= K with mass{key > P} < top_p * Z ----
     int P = K;
     if (p.top_p < 1.0f) {
-        float z = 0.f;
-        for (int i = tid; i < V; i += LSK_SAMPLE_THREADS) {
-            const float xi = x[i];
-            if (lsk_key16(xi) >= K) z += __expf((xi - m) * it);
-        }
-        z = block_sum(z, red);
-        const float budget = p.top_p * z;
+        const float budget = p.top_p * block_sum(mass_from(K), red);
         int lo = K, hi = key_max;                          // mass{key > key_max} = 0 < budget (top_p > 0); top_p <= 0 keeps the maximum only
         if (!(p.top_p > 0.f)) lo = key_max;
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
-            float g = 0.f;
-            for (int i = tid; i < V; i += LSK_SAMPLE_THREADS) {
-                const float xi = x[i];
-                if (lsk_key16(xi) > mid) g += __expf((xi - m) * it);
-            }
-            g = block_sum(g, red);
-            if (g < budget) hi = mid; else lo = mid + 1;
+            if (block_sum(mass_from(mid + 1), red) < budget) hi = mid; else lo = mid + 1;
         }
         P = lo;
     }
     // ---- normalise, write the probabilities, Gumbel-max draw ----
-    float z = 0.f;
-    for (int i = tid; i < V; i += LSK_SAMPLE_THREADS) {
-        const float xi = x[i];
-        if (lsk_key16(xi) >= P) z += __expf((xi - m) * it);
-    }
-    z = block_sum(z, red);
-    const float inv_z = 1.0f / z;
-    float best = -INFINITY;
-    int best_i = 0x7fffffff;
-    float* po = p.probs_out + (size_t)row * p.ld;
-    const int groups = (V + 3) >> 2;
-    for (int gq = tid; gq < groups; gq += LSK_SAMPLE_THREADS) {
-        unsigned int rnd[4];
-        lsk_philox4x32_10((unsigned int)gq, (unsigned int)(p.tag0 + row), p.off_lo, p.off_hi, p.seed_lo, p.seed_hi, rnd);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = gq * 4 + j;
-            if (i < V) {
-                const float xi = x[i];
-                const bool keep = lsk_key16(xi) >= P;
-                const float zi = (xi - m) * it;
-                po[i] = keep ? __expf(zi) * inv_z : 0.f;
-                const float s = keep ? zi + lsk_gumbel(rnd[j]) : -INFINITY;
-                if (s > best || (s == best && i < best_i)) { best = s; best_i = i; }
-            }
-        }
-    }
-    // a NaN row leaves no score above -inf (best_i stays 0x7fffffff): clamp like the greedy finalize kernel does, so that neither the
-    // stored token nor the embedding gather below can leave the vocabulary
-    const int tok = min(max(block_argmax(best, best_i, red, redi), 0), p.vocab - 1);
-    if (tid == 0) p.tokens_out[row] = tok;
-    if (row == 0 && p.embed_dst != nullptr) {
-        const elem8* src = (const elem8*)(p.embed + (size_t)tok * p.hidden);
-        elem8* dst = (elem8*)p.embed_dst;
-        for (int i = tid; i < p.hidden / 8; i += LSK_SAMPLE_THREADS) dst[i] = src[i];
-    }
+    const float inv_z = 1.0f / block_sum(mass_from(P), red);
+    SampleBest best;
+    for (int gq = tid; gq < (V + 3) >> 2; gq += LSK_SAMPLE_THREADS)
+        lsk_draw_quad(p, row, gq, lsk_quad_terms(lsk_load_quad(x, gq, V, 0.f, false), gq, V, P, m, it), inv_z, false, best);
+    lsk_sample_emit<LSK_SAMPLE_THREADS>(p, row, block_argmax(best, red, redi).idx);
+}
+
+__global__ __launch_bounds__(LSK_SAMPLE_THREADS) void lsk_sample_kernel(const SampleParams p) {
+    __shared__ float red[LSK_SAMPLE_WAVES];
+    __shared__ int redi[LSK_SAMPLE_WAVES];
+    static_assert(4 * LSK_SAMPLE_QUADS * LSK_SAMPLE_THREADS == LSK_SAMPLE_REG_VOCAB, "register path capacity");
+    if (p.vocab <= LSK_SAMPLE_REG_VOCAB && (p.ld & 3) == 0) lsk_sample_row_cached(p, blockIdx.x, red, redi);
+    else lsk_sample_row_reread(p, blockIdx.x, red, redi);
 }
 
 // ---- large vocabularies (V > 32 768: the llama3 family) ------------------------------------------------------------------------
@@ -405,17 +432,6 @@ __device__ __forceinline__ unsigned int lsk_ordered_bits(float x) {
 }
 __device__ __forceinline__ float lsk_from_ordered_bits(unsigned int o) {
     return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
-__device__ __forceinline__ float4 lsk_load_quad(const float* x, int gq, int V, float fill) {
-    float4 v = {fill, fill, fill, fill};
-    const int i0 = 4 * gq;
-    if (i0 + 3 < V) v = *(const float4*)(x + i0);
-    else {
-        if (i0 < V) v.x = x[i0];
-        if (i0 + 1 < V) v.y = x[i0 + 1];
-        if (i0 + 2 < V) v.z = x[i0 + 2];
-    }
-    return v;
 }
 
 __global__ __launch_bounds__(LSK_SAMPLE_THREADS) void lsk_sample_max_kernel(const SampleBigParams p) {
@@ -540,78 +556,42 @@ __global__ __launch_bounds__(LSK_SAMPLE_THREADS) void lsk_sample_scan_kernel(con
     for (int b = 0; b < BINS; ++b) { hist[b] = 0; if (count) cnt[b] = 0; }     // ... and so is the histogram
 }
 
-__global__ __launch_bounds__(LSK_SAMPLE_THREADS) void lsk_sample_draw_kernel(const SampleBigParams p) {
-    __shared__ float red[LSK_SAMPLE_WAVES];
-    __shared__ int redi[LSK_SAMPLE_WAVES];
-    const int row = blockIdx.y, V = p.s.vocab;
-    const float* x = p.s.logits + (size_t)row * p.s.ld;
-    float* po = p.s.probs_out + (size_t)row * p.s.ld;
-    const SampleRowState r = p.rows[row];
-    const float it = p.s.inv_temperature;
-    float best = -INFINITY;
-    int best_i = 0x7fffffff;
+// A workgroup's share of a spread row's draw, given the row's (P, max, 1 / Z_kept): probabilities written, its winner -> part_val / part_idx
+__device__ __forceinline__ void lsk_sample_draw_part(const SampleBigParams& b, int row, int P, float m, float inv_z, float* red, int* redi) {
+    const SampleParams& s = b.s;
+    const int V = s.vocab;
+    const float* x = s.logits + (size_t)row * s.ld;
+    SampleBest best;
     const int groups = (V + 3) >> 2;
-    for (int gq = blockIdx.x * LSK_SAMPLE_THREADS + threadIdx.x; gq < groups; gq += p.ns * LSK_SAMPLE_THREADS) {
-        const float4 v = lsk_load_quad(x, gq, V, 0.f);
-        const float xs[4] = {v.x, v.y, v.z, v.w};
-        unsigned int rnd[4];
-        lsk_philox4x32_10((unsigned int)gq, (unsigned int)(p.s.tag0 + row), p.s.off_lo, p.s.off_hi, p.s.seed_lo, p.s.seed_hi, rnd);
-        float pr[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = gq * 4 + j;
-            const bool keep = i < V && lsk_key16(xs[j]) >= r.P;
-            const float zi = (xs[j] - r.m) * it;
-            pr[j] = keep ? __expf(zi) * r.inv_z : 0.f;
-            const float sc = keep ? zi + lsk_gumbel(rnd[j]) : -INFINITY;
-            if (sc > best || (sc == best && i < best_i)) { best = sc; best_i = i; }
-        }
-        if (4 * gq + 3 < V) *(float4*)(po + 4 * gq) = float4{pr[0], pr[1], pr[2], pr[3]};
-        else
-            for (int j = 0; j < 4; ++j)
-                if (4 * gq + j < V) po[4 * gq + j] = pr[j];
-    }
-    // the workgroup's winner (lowest index on ties)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(best_i, o, 64);
-        if (ov > best || (ov == best && oi < best_i)) { best = ov; best_i = oi; }
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[w] = best; redi[w] = best_i; }
-    __syncthreads();
+    for (int gq = blockIdx.x * LSK_SAMPLE_THREADS + threadIdx.x; gq < groups; gq += b.ns * LSK_SAMPLE_THREADS)
+        lsk_draw_quad(s, row, gq, lsk_quad_terms(lsk_load_quad(x, gq, V, 0.f), gq, V, P, m, s.inv_temperature), inv_z, true, best);
+    best = block_argmax(best, red, redi);
     if (threadIdx.x == 0) {
-        float bv = red[0];
-        int bi = redi[0];
-        for (int i = 1; i < LSK_SAMPLE_WAVES; ++i)
-            if (red[i] > bv || (red[i] == bv && redi[i] < bi)) { bv = red[i]; bi = redi[i]; }
-        p.part_val[row * p.ns + blockIdx.x] = bv;
-        p.part_idx[row * p.ns + blockIdx.x] = bi;
+        b.part_val[row * b.ns + blockIdx.x] = best.val;
+        b.part_idx[row * b.ns + blockIdx.x] = best.idx;
     }
 }
 
-__global__ __launch_bounds__(256) void lsk_sample_pick_kernel(const SampleBigParams p) {
-    __shared__ int s_tok;
-    const int row = blockIdx.x;
-    if (threadIdx.x == 0) {
-        float bv = p.part_val[row * p.ns];
-        int bi = p.part_idx[row * p.ns];
-        for (int i = 1; i < p.ns; ++i) {
-            const float v = p.part_val[row * p.ns + i];
-            const int ix = p.part_idx[row * p.ns + i];
-            if (v > bv || (v == bv && ix < bi)) { bv = v; bi = ix; }
-        }
-        bi = min(max(bi, 0), p.s.vocab - 1);          // a NaN row: no partial ever beat -inf (index 0x7fffffff)
-        p.s.tokens_out[row] = bi;
-        s_tok = bi;
-    }
-    if (row != 0 || p.s.embed_dst == nullptr) return;
-    __syncthreads();
-    const elem8* src = (const elem8*)(p.s.embed + (size_t)s_tok * p.s.hidden);
-    elem8* dst = (elem8*)p.s.embed_dst;
-    for (int i = threadIdx.x; i < p.s.hidden / 8; i += 256) dst[i] = src[i];
+__global__ __launch_bounds__(LSK_SAMPLE_THREADS) void lsk_sample_draw_kernel(const SampleBigParams p) {
+    __shared__ float red[LSK_SAMPLE_WAVES];
+    __shared__ int redi[LSK_SAMPLE_WAVES];
+    const SampleRowState r = p.rows[blockIdx.y];
+    lsk_sample_draw_part(p, blockIdx.y, r.P, r.m, r.inv_z, red, redi);
 }
+
+// The row's winner among its ns partials (lowest index on ties), then the token tail.  One 256-thread workgroup per row.
+__device__ __forceinline__ void lsk_sample_pick_row(const SampleBigParams& b, int row) {
+    __shared__ int s_win;
+    if (threadIdx.x == 0) {
+        SampleBest w;
+        for (int i = 0; i < b.ns; ++i) lsk_best_update(w, b.part_val[row * b.ns + i], b.part_idx[row * b.ns + i]);
+        s_win = w.idx;
+    }
+    __syncthreads();
+    lsk_sample_emit<256>(b.s, row, s_win);
+}
+
+__global__ __launch_bounds__(256) void lsk_sample_pick_kernel(const SampleBigParams p) { lsk_sample_pick_row(p, blockIdx.x); }
 
 // ---- the same for top_k == 0 (the default) without 128 256 global atomics: two 256-bin levels, workgroup-private in LDS --------
 // (profile of the form above at llama3-8B: hist 42 us -- same-address 64-bit atomics from 32 workgroups serialise at the memory side --
@@ -770,9 +750,7 @@ __global__ __launch_bounds__(LSK_SAMPLE_THREADS) void lsk_sample_draw2_kernel(co
     __shared__ int s_P;
     __shared__ float s_inv_z;
     const SampleParams& s = p.b.s;
-    const int row = blockIdx.y, V = s.vocab;
-    const float* x = s.logits + (size_t)row * s.ld;
-    float* po = s.probs_out + (size_t)row * s.ld;
+    const int row = blockIdx.y;
     const float m = lsk_from_ordered_bits(p.b.rows[row].max_bits);
     if (threadIdx.x < 256) { c[threadIdx.x] = p.coarse[(size_t)row * 256 + threadIdx.x]; f[threadIdx.x] = p.fine[(size_t)row * 256 + threadIdx.x]; }
     __syncthreads();
@@ -797,101 +775,53 @@ __global__ __launch_bounds__(LSK_SAMPLE_THREADS) void lsk_sample_draw2_kernel(co
         }
     }
     __syncthreads();
-    const int P = s_P;
-    const float inv_z = s_inv_z, it = s.inv_temperature;
-    float best = -INFINITY;
-    int best_i = 0x7fffffff;
-    const int groups = (V + 3) >> 2;
-    for (int gq = blockIdx.x * LSK_SAMPLE_THREADS + threadIdx.x; gq < groups; gq += p.b.ns * LSK_SAMPLE_THREADS) {
-        const float4 v = lsk_load_quad(x, gq, V, 0.f);
-        const float xs[4] = {v.x, v.y, v.z, v.w};
-        unsigned int rnd[4];
-        lsk_philox4x32_10((unsigned int)gq, (unsigned int)(s.tag0 + row), s.off_lo, s.off_hi, s.seed_lo, s.seed_hi, rnd);
-        float pr[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = gq * 4 + j;
-            const bool keep = i < V && lsk_key16(xs[j]) >= P;
-            const float zi = (xs[j] - m) * it;
-            pr[j] = keep ? __expf(zi) * inv_z : 0.f;
-            const float sc = keep ? zi + lsk_gumbel(rnd[j]) : -INFINITY;
-            if (sc > best || (sc == best && i < best_i)) { best = sc; best_i = i; }
-        }
-        if (4 * gq + 3 < V) *(float4*)(po + 4 * gq) = float4{pr[0], pr[1], pr[2], pr[3]};
-        else
-            for (int j = 0; j < 4; ++j)
-                if (4 * gq + j < V) po[4 * gq + j] = pr[j];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(best_i, o, 64);
-        if (ov > best || (ov == best && oi < best_i)) { best = ov; best_i = oi; }
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[w] = best; redi[w] = best_i; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float bv = red[0];
-        int bi = redi[0];
-        for (int i = 1; i < LSK_SAMPLE_WAVES; ++i)
-            if (red[i] > bv || (red[i] == bv && redi[i] < bi)) { bv = red[i]; bi = redi[i]; }
-        p.b.part_val[row * p.b.ns + blockIdx.x] = bv;
-        p.b.part_idx[row * p.b.ns + blockIdx.x] = bi;
-    }
+    lsk_sample_draw_part(p.b, row, s_P, m, s_inv_z, red, redi);
 }
 
 // pick for the two-level form: the winner, then the row's state back to zero
 __global__ __launch_bounds__(256) void lsk_sample_pick2_kernel(const SampleTwoLevelParams p) {
-    __shared__ int s_tok;
-    const SampleBigParams& b = p.b;
     const int row = blockIdx.x;
     p.coarse[(size_t)row * 256 + threadIdx.x] = 0;
     p.fine[(size_t)row * 256 + threadIdx.x] = 0;
-    if (threadIdx.x == 0) {
-        float bv = b.part_val[row * b.ns];
-        int bi = b.part_idx[row * b.ns];
-        for (int i = 1; i < b.ns; ++i) {
-            const float v = b.part_val[row * b.ns + i];
-            const int ix = b.part_idx[row * b.ns + i];
-            if (v > bv || (v == bv && ix < bi)) { bv = v; bi = ix; }
-        }
-        bi = min(max(bi, 0), b.s.vocab - 1);          // a NaN row: no partial ever beat -inf (index 0x7fffffff)
-        b.s.tokens_out[row] = bi;
-        b.rows[row].max_bits = 0;
-        s_tok = bi;
-    }
-    if (row != 0 || b.s.embed_dst == nullptr) return;
-    __syncthreads();
-    const elem8* src = (const elem8*)(b.s.embed + (size_t)s_tok * b.s.hidden);
-    elem8* dst = (elem8*)b.s.embed_dst;
-    for (int i = threadIdx.x; i < b.s.hidden / 8; i += 256) dst[i] = src[i];
+    if (threadIdx.x == 0) p.b.rows[row].max_bits = 0;
+    lsk_sample_pick_row(p.b, row);
 }
 
 // Gumbel-max draw from max(q - p, 0) (max_fn, SSG:27-29; normalisation-free): the whole workgroup (LSK_SAMPLE_THREADS) takes part,
 // every thread returns the same index, 0x7fffffff when q <= p everywhere.  Shared by the one-GPU acceptance kernel and by rank 0 of the
 // layer pipeline (which holds p_n and receives q_n from the last rank): same stream, same arithmetic, same token.
 __device__ __forceinline__ int lsk_residual_draw(const float* __restrict__ q, const float* __restrict__ pd, int vocab, int tag_residual,
-                                                 unsigned int off_lo, unsigned int off_hi, unsigned int seed_lo, unsigned int seed_hi,
-                                                 float* red, int* redi) {
-    const int tid = threadIdx.x;
-    float best = -INFINITY;
-    int best_i = 0x7fffffff;
+                                                 const LskPhilox& rng, float* red, int* redi) {
+    SampleBest best;
     const int groups = (vocab + 3) >> 2;
-    for (int gq = tid; gq < groups; gq += LSK_SAMPLE_THREADS) {
+    for (int gq = threadIdx.x; gq < groups; gq += LSK_SAMPLE_THREADS) {
         unsigned int rnd[4];
-        lsk_philox4x32_10((unsigned int)gq, (unsigned int)tag_residual, off_lo, off_hi, seed_lo, seed_hi, rnd);
+        lsk_philox_words(rng, gq, tag_residual, rnd);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int i = gq * 4 + j;
             if (i < vocab) {
                 const float w = q[i] - pd[i];
-                const float s = (w > 0.f) ? __logf(w) + lsk_gumbel(rnd[j]) : -INFINITY;
-                if (s > best || (s == best && i < best_i)) { best = s; best_i = i; }
+                lsk_best_update(best, (w > 0.f) ? __logf(w) + lsk_gumbel(rnd[j]) : -INFINITY, i);
             }
         }
     }
-    return block_argmax(best, best_i, red, redi);
+    return block_argmax(best, red, redi).idx;
+}
+
+// The acceptance test (oracle: device_accept_test): how many of the `td` counted drafts are kept -- draft i while u_i < min(1, q_i(x_i) /
+// p_i(x_i)), u_i = word 0 of Philox counter (i, tag_accept).  One thread; probs(i, q, p) says where the two scalars of draft i are.
+template <class Probs>
+__device__ __forceinline__ int lsk_accept_test(int td, const LskPhilox& rng, int tag_accept, Probs&& probs) {
+    int n = 0;
+    for (int i = 0; i < td; ++i) {
+        float q, pd;
+        probs(i, q, pd);
+        unsigned int rnd[4];
+        lsk_philox_words(rng, i, tag_accept, rnd);
+        if (lsk_u01(rnd[0]) < fminf(1.0f, q / pd)) ++n; else break;
+    }
+    return n;
 }
 
 struct AcceptSampledParams {
@@ -905,8 +835,7 @@ struct AcceptSampledParams {
     const float* p_verify;      // [num_drafts + 1][ld]
     int ld;
     int vocab;
-    unsigned int seed_lo, seed_hi;
-    unsigned int off_lo, off_hi;
+    LskPhilox rng;
     int tag_accept;             // RNG tag of the acceptance uniforms (counter = draft index)
     int tag_residual;           // RNG tag of the residual draw
     StepState* st;
@@ -921,25 +850,17 @@ __global__ __launch_bounds__(LSK_SAMPLE_THREADS) void lsk_accept_sampled_kernel(
     int td_w0 = 0;
     if (tid < 64) td_w0 = lsk_drafts_until_eos(p.draft, p.num_drafts, p.eos, p.n_eos);   // wave 0: a drafted EOS ends the draft (SSG:146-148)
     if (tid == 0) {
-        const int td = td_w0;
-        int n = 0;
-        for (int i = 0; i < td; ++i) {
-            const int tok = p.draft[i];
-            const float q = p.p_verify[(size_t)i * p.ld + tok];
-            const float pd = p.p_draft[(size_t)i * p.ld + tok];
-            unsigned int rnd[4];
-            lsk_philox4x32_10((unsigned int)i, (unsigned int)p.tag_accept, p.off_lo, p.off_hi, p.seed_lo, p.seed_hi, rnd);
-            if (lsk_u01(rnd[0]) < fminf(1.0f, q / pd)) ++n; else break;
-        }
-        s_td = td;
-        s_n = n;
+        s_td = td_w0;
+        s_n = lsk_accept_test(td_w0, p.rng, p.tag_accept, [&](int i, float& q, float& pd) {
+            q = p.p_verify[(size_t)i * p.ld + p.draft[i]];
+            pd = p.p_draft[(size_t)i * p.ld + p.draft[i]];
+        });
     }
     __syncthreads();
     const int td = s_td, n = s_n;
     int next;
     if (n < td) {
-        next = lsk_residual_draw(p.p_verify + (size_t)n * p.ld, p.p_draft + (size_t)n * p.ld, p.vocab, p.tag_residual, p.off_lo, p.off_hi,
-                                 p.seed_lo, p.seed_hi, red, redi);
+        next = lsk_residual_draw(p.p_verify + (size_t)n * p.ld, p.p_draft + (size_t)n * p.ld, p.vocab, p.tag_residual, p.rng, red, redi);
         if (next == 0x7fffffff) next = p.draft[n];   // q == p on the whole row: cannot be reached through a rejection
     } else {
         next = p.verified[td];
@@ -966,20 +887,6 @@ __global__ __launch_bounds__(LSK_SAMPLE_THREADS) void lsk_accept_sampled_kernel(
     }
 }
 
-// The acceptance of one sampled step (host side): drafts draft[0..num_drafts) with their distributions p_draft against the verify
-// tokens and distributions; state (optional) receives the rollback and the next input token.  The caller checks the launch.
-static inline void launch_accept_sampled(int* draft, int* verified, int num_drafts, const int* eos, int n_eos, int prompt_len,
-                                         const float* p_draft, const float* p_verify, int ld, int vocab, uint64_t seed, uint64_t offset,
-                                         StepState* state, int* result, hipStream_t st) {
-    AcceptSampledParams ap{};
-    ap.draft = draft; ap.verified = verified; ap.num_drafts = num_drafts; ap.eos = eos; ap.n_eos = n_eos; ap.prompt_len = prompt_len;
-    ap.p_draft = p_draft; ap.p_verify = p_verify; ap.ld = ld; ap.vocab = vocab;
-    ap.seed_lo = (unsigned int)seed; ap.seed_hi = (unsigned int)(seed >> 32);
-    ap.off_lo = (unsigned int)offset; ap.off_hi = (unsigned int)(offset >> 32);
-    ap.tag_accept = LSK_TAG_ACCEPT; ap.tag_residual = LSK_TAG_RESIDUAL; ap.st = state; ap.result = result;
-    hipLaunchKernelGGL(lsk_accept_sampled_kernel, dim3(1), dim3(LSK_SAMPLE_THREADS), 0, st, ap);
-}
-
 // ---- sample=True on the layer pipeline (SURVEY 8e x 8f N2) -----------------------------------------------------------------------
 // The one-GPU acceptance kernel above needs, per draft i, the two scalars q_i(x_i) and p_i(x_i), and at the first rejection the two
 // ROWS q_n and p_n.  On the pipeline p lives on rank 0 (the draft loop) and q on the last rank (the verify head), so the test is split
@@ -1001,8 +908,7 @@ struct PipeAcceptSampledParams {
     int n_eos;
     const float* p_verify;      // [rows][ld]
     int ld;
-    unsigned int seed_lo, seed_hi;
-    unsigned int off_lo, off_hi;
+    LskPhilox rng;
     int tag_accept;
     StepState* st;
     int* result;                // LSK_PRES_QROW + ld words
@@ -1017,16 +923,12 @@ __global__ __launch_bounds__(LSK_SAMPLE_THREADS) void lsk_pipeline_accept_sample
     int td_w0 = 0;
     if (tid < 64) td_w0 = lsk_drafts_until_eos(draft, num_drafts, p.eos, p.n_eos);      // wave 0: a drafted EOS ends the draft (SSG:146-148)
     if (tid == 0) {
-        const bool out_of_step = hdr[LSK_HDR_MODE] != 1 || (unsigned int)hdr[LSK_HDR_OFF_LO] != p.off_lo || (unsigned int)hdr[LSK_HDR_OFF_HI] != p.off_hi;
+        const bool out_of_step = hdr[LSK_HDR_MODE] != 1 || (unsigned int)hdr[LSK_HDR_OFF_LO] != p.rng.off_lo || (unsigned int)hdr[LSK_HDR_OFF_HI] != p.rng.off_hi;
         const int td = td_w0;
-        int n = 0;
-        for (int i = 0; i < td; ++i) {
-            const float q = p.p_verify[(size_t)i * p.ld + draft[i]];
-            const float pd = __builtin_bit_cast(float, hdr[LSK_HDR_PDRAFT + i]);
-            unsigned int rnd[4];
-            lsk_philox4x32_10((unsigned int)i, (unsigned int)p.tag_accept, p.off_lo, p.off_hi, p.seed_lo, p.seed_hi, rnd);
-            if (lsk_u01(rnd[0]) < fminf(1.0f, q / pd)) ++n; else break;
-        }
+        const int n = lsk_accept_test(td, p.rng, p.tag_accept, [&](int i, float& q, float& pd) {
+            q = p.p_verify[(size_t)i * p.ld + draft[i]];
+            pd = __builtin_bit_cast(float, hdr[LSK_HDR_PDRAFT + i]);       // p_i(x_i) travelled in the header
+        });
         s_n = n;
         const int next = (n == td) ? p.verified[td] : -1;
         for (int i = 0; i < n; ++i) p.result[LSK_RES_EMIT + i] = draft[i];
@@ -1050,14 +952,12 @@ __global__ __launch_bounds__(LSK_SAMPLE_THREADS) void lsk_pipeline_accept_sample
 
 // rank 0: finish a received result block whose residual draw is pending -- the token from max(q_n - p_n, 0), with the p_n of ITS draft loop
 __global__ __launch_bounds__(LSK_SAMPLE_THREADS) void lsk_pipeline_residual_kernel(int* __restrict__ blk, const float* __restrict__ p_draft, int ld, int vocab,
-                                                                                   const int* __restrict__ draft, unsigned int seed_lo, unsigned int seed_hi,
-                                                                                   unsigned int off_lo, unsigned int off_hi, int tag_residual) {
+                                                                                   const int* __restrict__ draft, const LskPhilox rng, int tag_residual) {
     __shared__ float red[LSK_SAMPLE_WAVES];
     __shared__ int redi[LSK_SAMPLE_WAVES];
     if (!blk[LSK_PRES_PENDING]) return;                       // uniform over the workgroup
     const int n = min(max(blk[0], 0), LSK_ROWS - 1);
-    int next = lsk_residual_draw((const float*)(blk + LSK_PRES_QROW), p_draft + (size_t)n * ld, vocab, tag_residual, off_lo, off_hi, seed_lo, seed_hi,
-                                 red, redi);
+    int next = lsk_residual_draw((const float*)(blk + LSK_PRES_QROW), p_draft + (size_t)n * ld, vocab, tag_residual, rng, red, redi);
     if (next == 0x7fffffff) next = draft[n];
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1065,4 +965,86 @@ __global__ __launch_bounds__(LSK_SAMPLE_THREADS) void lsk_pipeline_residual_kern
         blk[LSK_RES_EMIT + n] = next;
         blk[LSK_PRES_PENDING] = 0;
     }
+}
+
+// ---- host side: each launch built once, for the engine (lsk_generate.hip) and the test library (lsk_test_exports.hip) ----------------
+// The launchers take plain pointers and sizes (the engine only for its samp_* workspace); the caller has checked them.
+//
+// The large-vocabulary draw is a SEQUENCE of launches that hand histograms, row maxima and row states to each other and leave them zero
+// for the next draw (the last kernel of the sequence clears what the others filled).  If a launch of the sequence fails, the ones
+// behind it never run and the state stays dirty -- every later draw would silently use wrong masses.  So a failed sequence zeroes
+// the whole state before the error is returned.
+static int sample_sequence_status(lsk_engine* e, hipStream_t st) {
+    const hipError_t err = hipGetLastError();
+    if (err == hipSuccess) return 0;
+    if (e->samp_hist != nullptr && e->samp_state_bytes) (void)hipMemsetAsync(e->samp_hist, 0, e->samp_state_bytes, st);
+    return lsk_fail("sample=True: a launch of the draw sequence failed: %s (sampling state cleared)", hipGetErrorString(err));
+}
+
+// m rows of `logits` [m][ld] over `vocab` entries drawn under (seed, offset) with tags tag0, tag0 + 1, ...: tokens -> tokens_dev, warped
+// distributions -> probs [m][ld]; embed_dst (optional) receives row `tokens_dev[0]` of the [vocab][hidden] table `embed`
+static int launch_sample(lsk_engine* e, const float* logits, int ld, int vocab, int m, float temperature, int top_k, float top_p, uint64_t seed,
+                         uint64_t offset, int tag0, int* tokens_dev, float* probs, const elem_t* embed, int hidden, elem_t* embed_dst, hipStream_t st) {
+    SampleParams sp{};
+    sp.logits = logits; sp.ld = ld; sp.vocab = vocab; sp.inv_temperature = 1.0f / temperature;
+    sp.top_k = top_k; sp.top_p = top_p; sp.rng = lsk_philox_of(seed, offset);
+    sp.tag0 = tag0; sp.tokens_out = tokens_dev; sp.probs_out = probs;
+    sp.embed = embed; sp.hidden = hidden; sp.embed_dst = embed_dst;
+    if (vocab <= LSK_SAMPLE_REG_VOCAB || e->samp_hist == nullptr || (ld & 3)) {
+        hipLaunchKernelGGL(lsk_sample_kernel, dim3(m), dim3(LSK_SAMPLE_THREADS), 0, st, sp);
+        HIP_OK(hipGetLastError());
+        return 0;
+    }
+    // large vocabularies: the row spread over ns workgroups
+    SampleBigParams bp{};
+    bp.s = sp; bp.hist = e->samp_hist; bp.cnt = e->samp_cnt; bp.rows = (SampleRowState*)e->samp_rows;
+    bp.part_val = e->samp_part_val; bp.part_idx = e->samp_part_idx;
+    const int groups = (vocab + 3) / 4;
+    bp.ns = (groups + LSK_SAMPLE_THREADS - 1) / LSK_SAMPLE_THREADS;
+    if (bp.ns > 64) bp.ns = 64;
+    if (m > LSK_MAX_ROWS + 1) return lsk_fail("launch_sample: %d rows", m);
+    const dim3 wide(bp.ns, m), one(1, m);
+    hipLaunchKernelGGL(lsk_sample_max_kernel, wide, dim3(LSK_SAMPLE_THREADS), 0, st, bp);
+    if (!(top_k > 0 && top_k < vocab)) {                        // no top-k (the default): the two-level form
+        SampleTwoLevelParams tp{};
+        tp.b = bp; tp.coarse = e->samp_coarse; tp.fine = e->samp_coarse + (size_t)(LSK_MAX_ROWS + 1) * 256;
+        hipLaunchKernelGGL(lsk_sample_coarse_kernel, wide, dim3(LSK_SAMPLE_THREADS), 0, st, tp);
+        hipLaunchKernelGGL(lsk_sample_fine_kernel, wide, dim3(LSK_SAMPLE_THREADS), 0, st, tp);
+        hipLaunchKernelGGL(lsk_sample_draw2_kernel, wide, dim3(LSK_SAMPLE_THREADS), 0, st, tp);
+        hipLaunchKernelGGL(lsk_sample_pick2_kernel, dim3(m), dim3(256), 0, st, tp);
+        return sample_sequence_status(e, st);
+    }
+    hipLaunchKernelGGL(lsk_sample_hist_kernel, wide, dim3(LSK_SAMPLE_THREADS), 0, st, bp);
+    hipLaunchKernelGGL(lsk_sample_scan_kernel, one, dim3(LSK_SAMPLE_THREADS), 0, st, bp);
+    hipLaunchKernelGGL(lsk_sample_draw_kernel, wide, dim3(LSK_SAMPLE_THREADS), 0, st, bp);
+    hipLaunchKernelGGL(lsk_sample_pick_kernel, dim3(m), dim3(256), 0, st, bp);
+    return sample_sequence_status(e, st);
+}
+
+// The acceptance of one sampled step: drafts draft[0..num_drafts) with their distributions p_draft against the verify tokens and
+// distributions; state (optional) receives the rollback and the next input token.  The caller checks the launch (this and the two below).
+static inline void launch_accept_sampled(int* draft, int* verified, int num_drafts, const int* eos, int n_eos, int prompt_len,
+                                         const float* p_draft, const float* p_verify, int ld, int vocab, uint64_t seed, uint64_t offset,
+                                         StepState* state, int* result, hipStream_t st) {
+    AcceptSampledParams ap{};
+    ap.draft = draft; ap.verified = verified; ap.num_drafts = num_drafts; ap.eos = eos; ap.n_eos = n_eos; ap.prompt_len = prompt_len;
+    ap.p_draft = p_draft; ap.p_verify = p_verify; ap.ld = ld; ap.vocab = vocab; ap.rng = lsk_philox_of(seed, offset);
+    ap.tag_accept = LSK_TAG_ACCEPT; ap.tag_residual = LSK_TAG_RESIDUAL; ap.st = state; ap.result = result;
+    hipLaunchKernelGGL(lsk_accept_sampled_kernel, dim3(1), dim3(LSK_SAMPLE_THREADS), 0, st, ap);
+}
+
+// the pipeline's last rank: the acceptance test over the message `msg` against the verify draws, result block (and q_n) -> result
+static inline void launch_pipeline_accept_sampled(const elem_t* msg, const int* verified, const int* eos, int n_eos, const float* p_verify, int ld,
+                                                  uint64_t seed, uint64_t offset, StepState* state, int* result, hipStream_t st) {
+    PipeAcceptSampledParams ap{};
+    ap.msg = msg; ap.verified = verified; ap.eos = eos; ap.n_eos = n_eos; ap.p_verify = p_verify; ap.ld = ld;
+    ap.rng = lsk_philox_of(seed, offset); ap.tag_accept = LSK_TAG_ACCEPT; ap.st = state; ap.result = result;
+    hipLaunchKernelGGL(lsk_pipeline_accept_sampled_kernel, dim3(1), dim3(LSK_SAMPLE_THREADS), 0, st, ap);
+}
+
+// the pipeline's rank 0: the pending residual draw of result block `blk` with its own draft rows p_draft (drafts in `draft`)
+static inline void launch_pipeline_residual(int* blk, const float* p_draft, int ld, int vocab, const int* draft, uint64_t seed, uint64_t offset,
+                                            hipStream_t st) {
+    hipLaunchKernelGGL(lsk_pipeline_residual_kernel, dim3(1), dim3(LSK_SAMPLE_THREADS), 0, st, blk, p_draft, ld, vocab, draft,
+                       lsk_philox_of(seed, offset), LSK_TAG_RESIDUAL);
 }

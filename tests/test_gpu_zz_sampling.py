@@ -93,6 +93,74 @@ def test_sample_rows_of_a_128k_vocabulary_match_the_model(gpu_device, temperatur
     eng.close()
 
 
+def test_sample_rows_of_an_unaligned_buffer_match_the_model_draw_for_draw(gpu_device):
+    """A caller-owned buffer whose leading dimension is no multiple of 4 (row 1 starts off 16-byte alignment) takes the one-workgroup
+    form that re-reads the row from memory instead of holding it in registers: same kept set, probabilities and draws."""
+    from oracle import sampling_oracle as so
+    rec = next(c for c in CASES if c["vocab"] == 1000)
+    V, ld = 1000, 1003
+    model, eng = _engine(V, gpu_device)
+    rows = np.stack([np.asarray(rec["draft_logits"], dtype=np.float32), np.asarray(rec["verify_logits"], dtype=np.float32)])
+    logits = torch.zeros(2, ld, dtype=torch.float32)
+    logits[:, :V] = torch.tensor(rows)
+    logits = logits.to(gpu_device)
+    assert logits.stride(0) == ld and ld % 4 != 0
+    mismatches = total = 0
+    for offset in range(10):
+        toks, probs = eng.sample_rows(logits, rec["temperature"], rec["top_k"], rec["top_p"], seed=4242, offset=offset, tag0=5)
+        toks, probs = toks.cpu().tolist(), probs.cpu().numpy()
+        for r in range(2):
+            want_tok, want_probs = so.device_sample_row(rows[r], rec["temperature"], rec["top_k"], rec["top_p"], 4242, offset, 5 + r)
+            assert ((probs[r, :V] > 0) == (want_probs > 0)).all()
+            assert np.allclose(probs[r, :V], want_probs, rtol=0, atol=2e-6)
+            assert want_probs[toks[r]] > 0
+            total += 1
+            mismatches += int(toks[r] != want_tok)      # fast-math log/exp can flip a near-tie of two Gumbel scores
+    assert mismatches <= max(1, total // 25), (mismatches, total)
+    eng.close()
+
+
+def test_sample_rows_of_an_unaligned_128k_buffer_match_the_model(gpu_device):
+    """The same at the llama3 vocabulary: ld = V + 1 keeps the draw off the multi-workgroup forms, so one workgroup re-reads a
+    128 256-logit row (top-k and top-p both searched by bisection over memory)."""
+    from layerskip_amd import synthetic
+    from layerskip_amd.engine import HipEngine
+    from oracle import sampling_oracle as so
+    temperature, top_k, top_p = 1.0, 50, 0.95
+    cfg = synthetic.make_config("slice-1B")
+    model = synthetic.build_model(cfg, seed=0, exit_layer=2, late_damping=0.1, dtype=torch.bfloat16, device=gpu_device, gen_device=gpu_device)
+    eng = HipEngine(model, max_ctx=256, max_prompt=32)
+    g = torch.Generator().manual_seed(77)
+    V = cfg.vocab_size
+    ld = V + 1
+    assert V > 32768 and ld % 4 != 0
+    rows = torch.stack([(torch.randn(V, generator=g) * 2.0), (torch.randn(V, generator=g) * 3.5 - 1.0), (torch.randn(V, generator=g) * 0.7)])
+    rows = rows.to(torch.bfloat16).float()                   # logits are bf16-exact, as the lm_head produces them
+    rows[1, 777] = rows[1].max() + 4.0                        # one row with a dominant token
+    logits = torch.zeros(3, ld, dtype=torch.float32)
+    logits[:, :V] = rows
+    logits = logits.to(gpu_device)
+    rows_np = rows.numpy()
+    warped = [so.device_warp(rows_np[r], temperature, top_k, top_p) for r in range(3)]
+    mismatches = total = 0
+    for offset in range(2):
+        toks, probs = eng.sample_rows(logits, temperature, top_k, top_p, seed=99, offset=offset, tag0=3)
+        toks, probs = toks.cpu().tolist(), probs.cpu().numpy()
+        for r in range(3):
+            keep, want_probs = warped[r]
+            assert ((probs[r, :V] > 0) == (want_probs > 0)).all(), (r, offset, int((probs[r, :V] > 0).sum()), int(keep.sum()))
+            assert np.allclose(probs[r, :V], want_probs, rtol=0, atol=2e-6)
+            x = rows_np[r]
+            z = ((x - x.max()) * np.float32(1.0 / temperature)).astype(np.float32)
+            u = so.device_uniforms(V, 3 + r, 99, offset)
+            score = np.where(keep, z.astype(np.float64) - np.log(-np.log(u.astype(np.float64))), -np.inf)
+            assert want_probs[toks[r]] > 0
+            total += 1
+            mismatches += int(toks[r] != int(np.argmax(score)))
+    assert mismatches <= max(1, total // 25), (mismatches, total)
+    eng.close()
+
+
 @pytest.mark.parametrize("temperature,top_k,top_p", [(0.7, 5, 1.0), (1.0, 0, 0.6), (0.9, 12, 0.8)])
 def test_fp16_library_filters_at_fp16_resolution(gpu_device, temperature, top_k, top_p):
     """The -DLSK_ELEM_F16 library: logits are fp16 values, whose 10-bit mantissa the bf16-shaped key (upper half of the fp32 pattern)
