@@ -43,7 +43,9 @@ extern "C" {
                              the workspace's eos region grew with it); vocabularies that are not a multiple of 16 documented as supported
                              5: sample=True autoregressive decoding on the device (lsk_ar_generate_sampled, lsk_ar_step_sampled)
                              6: opt-in FP8 (e4m3) weight storage (lsk_packed_bytes_fp8, lsk_pack_linear_fp8, lsk_engine_set_weight_format,
-                             lsk_engine_set_layer_prefill) */
+                             lsk_engine_set_layer_prefill); version 6 also covers the opt-in MXFP4 weight storage, whose entry
+                             points are additive (lsk_packed_bytes_mxfp4, lsk_pack_linear_mxfp4, lsk_engine_set_prefill_scratch,
+                             LSK_WEIGHT_FORMAT_MXFP4) */
 #define LSK_MAX_ROWS 16
 #define LSK_MAX_SPEC 15   /* num_speculations handled by one fused step (rows = spec + 1) */
 #define LSK_MAX_EOS 1024   /* eos + stop token ids of one generation (generator_base.py:106); ids outside the vocabulary are dropped by the host */
@@ -122,6 +124,29 @@ int lsk_packed_bytes_fp8(int32_t n_rows, int32_t k, size_t* out_bytes);
 int lsk_pack_linear_fp8(const void* src, int32_t n_rows, int32_t k, int32_t ld_src, void* dst, int32_t dst_rows,
                         int32_t dst_tile_offset, int32_t dst_tile_stride, int32_t rope_head_dim, void* stream);
 
+/* ---- MXFP4 (OCP e2m1 codes, one E8M0 exponent per 32-feature block) weight storage, opt-in, bf16 library only (the fp16 / fp32
+ * libraries export the symbols and return an error).  For q/k/v, o_proj, gate/up and down; the lm_head of such an engine is FP8 (above).
+ * Format (specification: layerskip_amd/quant.py quantize_blocks, which lsk_pack_linear_mxfp4 agrees with bit for bit): a block is 32
+ * consecutive input features of one output row; e = the smallest integer with amax_block <= 6 * 2^e, clamped to [-125, 124], 0 for an
+ * all-zero block, stored as the byte e + 127; code = e2m1(w / 2^e), round to nearest, ties to the even code (bit 3 sign, bits 2:1
+ * exponent, bit 0 mantissa: 0, 0.5, 1, 1.5, 2, 3, 4, 6); a value that rounds to zero has code 0.  code * 2^e is exact in bf16, and
+ * the kernels widen the codes in front of the same MFMA in the same order, so an engine on MXFP4 buffers computes BIT FOR BIT what the
+ * bf16 engine computes on the dequantised weights.
+ * Buffer of n_rows x k (rows16 = n_rows rounded up to 16): the tiles of lsk_pack_linear with 4-bit elements (rows16 * k / 2 bytes; a
+ * tile's k-step is 256 B, lane l owns 4 B = the eight codes of row l % 16, features 8 (l / 16) .. + 8, element i in byte i / 2, low
+ * nibble first), then the exponent table: one byte per (PACKED row, k-step), row-major.  lsk_packed_bytes_mxfp4 returns
+ * rows16 * k / 2 + rows16 * k / 32 plus the table's padding: a row of the table is k / 32 rounded up to a multiple of 4 bytes, and 16
+ * bytes follow the last row (a lane of the decode kernel fetches the exponents of its wave's <= 16 consecutive k-steps as one aligned
+ * 20-byte window).  Padded rows: code 0, exponent byte 127; so is every padding byte of the table.
+ * lsk_pack_linear_mxfp4 takes lsk_pack_linear_fp8's arguments; it never synchronises.
+ * Prefill: there is no prefill kernel that reads the codes.  The engine widens one layer's four projections at a time into a caller-
+ * owned scratch in the packed model-dtype layout -- lsk_engine_set_prefill_scratch: at least the sum of lsk_packed_bytes over wqkv, wo,
+ * wgu and wdown, 256-byte aligned; NULL unbinds -- and the model-dtype prefill kernels read that.  lsk_engine_set_layer_prefill keeps
+ * its meaning as a per-layer override and takes precedence. */
+int lsk_packed_bytes_mxfp4(int32_t n_rows, int32_t k, size_t* out_bytes);
+int lsk_pack_linear_mxfp4(const void* src, int32_t n_rows, int32_t k, int32_t ld_src, void* dst, int32_t dst_rows,
+                          int32_t dst_tile_offset, int32_t dst_tile_stride, int32_t rope_head_dim, void* stream);
+
 /* ---- engine lifetime ---------------------------------------------------------------------- */
 int lsk_engine_create(const lsk_config* cfg, void* workspace, size_t workspace_bytes,
                       void* kv_pool, size_t kv_pool_bytes, lsk_engine** out);
@@ -148,7 +173,9 @@ int lsk_engine_set_layer(lsk_engine* e, int32_t layer, const void* wqkv, const v
  * the path FP8 engines took before the prefill kernel read the codes, kept as the in-process A/B lever of tools/fp8_prefill_ab.py. */
 #define LSK_WEIGHT_FORMAT_ELEM 0       /* model dtype (default) */
 #define LSK_WEIGHT_FORMAT_FP8_E4M3 1
+#define LSK_WEIGHT_FORMAT_MXFP4 2      /* wqkv / wo / wgu / wdown: lsk_pack_linear_mxfp4; lm_head: lsk_pack_linear_fp8 */
 int lsk_engine_set_weight_format(lsk_engine* e, int32_t weight_format);
+int lsk_engine_set_prefill_scratch(lsk_engine* e, void* scratch, size_t scratch_bytes);
 int lsk_engine_set_layer_prefill(lsk_engine* e, int32_t layer, const void* wqkv, const void* wo, const void* wgu, const void* wdown);
 /* embed: plain bf16 [V][H]; final_norm: bf16 [H]; lm_head: PACKED [V][H] -- each may be NULL on a pipeline rank that never embeds a
  * token / runs a head (a middle rank: checkpoint.load_layer_range(embed=False, head=False)); the entry points that need them say so;

@@ -18,7 +18,7 @@ LSK_OPT_TARGET_WGS = 2
 LSK_OPT_FUSED_ATTN = 3
 LSK_OPT_FLASH_PREFILL = 5
 LSK_OPT_GRAPH_STEPS = 7       # steady-state greedy steps replayed from hipGraphs (default off)
-WEIGHT_FORMATS = {"bf16": 0, "fp8_e4m3": 1}    # HipEngine(weight_format=...) -> LSK_WEIGHT_FORMAT_* ("bf16": the model dtype, the default)
+WEIGHT_FORMATS = {"bf16": 0, "fp8_e4m3": 1, "mxfp4": 2}    # HipEngine(weight_format=...) -> LSK_WEIGHT_FORMAT_* ("bf16": the model dtype, the default)
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(_CSRC, "liblayerskip_hip.so")            # bf16 build (BASELINE configs)
@@ -57,7 +57,10 @@ PROTOTYPES = {
     "lsk_pack_linear": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "lsk_packed_bytes_fp8": (c_int32, [c_int32, c_int32, POINTER(c_size_t)]),
     "lsk_pack_linear_fp8": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "lsk_packed_bytes_mxfp4": (c_int32, [c_int32, c_int32, POINTER(c_size_t)]),
+    "lsk_pack_linear_mxfp4": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "lsk_engine_set_weight_format": (c_int32, [c_void_p, c_int32]),
+    "lsk_engine_set_prefill_scratch": (c_int32, [c_void_p, c_void_p, c_size_t]),
     "lsk_engine_set_layer_prefill": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsk_engine_create": (c_int32, [POINTER(LskConfig), c_void_p, c_size_t, c_void_p, c_size_t, POINTER(c_void_p)]),
     "lsk_engine_destroy": (c_int32, [c_void_p]),

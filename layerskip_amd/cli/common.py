@@ -33,6 +33,7 @@ class SyntheticArguments:
     device: str = "cuda:0"
     pp_balance: str = "draft"          # multi-GPU (torchrun) layer split: "draft" | "memory" (layerskip_amd.pipeline.plan_partition)
     weight_format: str = "bf16"        # "fp8_e4m3": projections stored as e4m3 codes + one power of two per row (layerskip_amd/quant.py)
+                                       # "mxfp4": q/k/v/o/gate/up/down as e2m1 codes + one power of two per 32-feature block, lm_head FP8
 
 
 def setup(args: Arguments, syn: SyntheticArguments):

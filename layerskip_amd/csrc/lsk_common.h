@@ -183,7 +183,7 @@ struct GemmParams {
     int M;                  // 1..16
     int K;                  // multiple of 32
     const elem_t* wp;       // packed weight tiles [n_tiles][K/32][64][8]
-    unsigned wp_bytes;      // bytes of the tiles (FP8 format: of the codes; the rows' fp32 powers of two follow them)
+    unsigned wp_bytes;      // bytes of the tiles (FP8 / MXFP4 format: of the codes; the scale table follows them)
     int N;                  // logical output features (rows of the nn.Linear weight)
     int n_tiles;            // ceil(N / 16)
     int tiles_per_wg;       // <= 8 (<= 16 for SWIGLU: 8 gate/up pairs; any number for EPI_HEAD when K is one chunk): set by launch_gemm
@@ -216,7 +216,7 @@ struct GemmParams {
     int ld_logits;
     float* part_val;        // [grid][16]
     int* part_idx;          // [grid][16]
-    int wfmt;               // host side only: format of wp (LSK_WF_ELEM | LSK_WF_FP8, lsk_gemm.h) -- picks the kernel instance
+    int wfmt;               // host side only: format of wp (LSK_WF_ELEM | LSK_WF_FP8 | LSK_WF_MXFP4, lsk_gemm.h) -- picks the kernel instance
     LSK_TRACE_FIELD
 };
 

@@ -20,6 +20,7 @@ struct lsk_engine {
     const elem_t *embed = nullptr, *final_norm = nullptr, *lm_head = nullptr, *rope_cos = nullptr, *rope_sin = nullptr;
     int rope_len = 0;
     int weight_format = 0;        // LSK_WEIGHT_FORMAT_*: what wqkv / wo / wgu / wdown / lm_head point at (lsk_engine_set_weight_format)
+    elem_t* pf_scratch = nullptr; // MXFP4: caller-owned scratch of one layer's four projections in the packed model-dtype layout (prefill)
     // device workspace carve
     unsigned char* ws = nullptr;
     size_t ws_bytes = 0;

@@ -151,6 +151,35 @@ extern "C" int lsk_pack_linear_fp8(const void* src, int32_t n_rows, int32_t k, i
 #endif
 }
 
+// codes (rows16 * k / 2), then the exponent table: lsk_mxfp4_ksp(k) bytes per packed row and 16 bytes behind the last row
+static size_t mxfp4_bytes(size_t rows16, int k) { return rows16 * (size_t)(k >> 1) + rows16 * (size_t)lsk_mxfp4_ksp(k) + 16; }
+
+extern "C" int lsk_packed_bytes_mxfp4(int32_t n_rows, int32_t k, size_t* out_bytes) {
+    if (!out_bytes) return lsk_fail("lsk_packed_bytes_mxfp4: null out");
+    if (n_rows <= 0 || k <= 0 || (k % 32)) return lsk_fail("lsk_packed_bytes_mxfp4: n_rows=%d k=%d (k must be a multiple of 32)", n_rows, k);
+    *out_bytes = mxfp4_bytes((size_t)((n_rows + 15) / 16) * 16, k);
+    return 0;
+}
+
+extern "C" int lsk_pack_linear_mxfp4(const void* src, int32_t n_rows, int32_t k, int32_t ld_src, void* dst, int32_t dst_rows,
+                                     int32_t dst_tile_offset, int32_t dst_tile_stride, int32_t rope_head_dim, void* stream) {
+#if LSK_ELEM_DTYPE == 0
+    if (!src || !dst) return lsk_fail("lsk_pack_linear_mxfp4: null pointer");
+    if (n_rows <= 0 || k <= 0 || (k % 32)) return lsk_fail("lsk_pack_linear_mxfp4: k=%d must be a positive multiple of 32", k);
+    if (rope_head_dim > 0 && ((rope_head_dim % 32) || (n_rows % rope_head_dim))) return lsk_fail("lsk_pack_linear_mxfp4: bad rope_head_dim");
+    const int n_tiles = (n_rows + 15) / 16;
+    if (dst_rows <= 0 || (dst_rows % 16) || dst_tile_offset < 0 || dst_tile_stride < 1 ||
+        (long long)dst_tile_offset + (long long)(n_tiles - 1) * dst_tile_stride >= dst_rows / 16)
+        return lsk_fail("lsk_pack_linear_mxfp4: tiles %d + %d x %d do not fit a destination of %d rows", dst_tile_offset, n_tiles, dst_tile_stride, dst_rows);
+    hipLaunchKernelGGL(lsk_pack_mxfp4_kernel, dim3((unsigned)n_tiles * 16), dim3(256), 0, (hipStream_t)stream, (const elem_t*)src, n_rows, k,
+                       ld_src, (unsigned char*)dst, dst_rows, dst_tile_offset, dst_tile_stride, rope_head_dim);
+    HIP_OK(hipGetLastError());
+    return 0;
+#else
+    return lsk_fail("lsk_pack_linear_mxfp4: MXFP4 weight storage exists in the bf16 library only");
+#endif
+}
+
 extern "C" int lsk_engine_destroy(lsk_engine* e);
 
 extern "C" int lsk_engine_create(const lsk_config* cfg, void* workspace, size_t workspace_bytes, void* kv_pool, size_t kv_pool_bytes,
@@ -248,10 +277,10 @@ extern "C" int lsk_engine_set_layer(lsk_engine* e, int32_t layer, const void* wq
 
 extern "C" int lsk_engine_set_weight_format(lsk_engine* e, int32_t weight_format) {
     if (!e) return lsk_fail("lsk_engine_set_weight_format: null engine");
-    if (weight_format != LSK_WEIGHT_FORMAT_ELEM && weight_format != LSK_WEIGHT_FORMAT_FP8_E4M3)
+    if (weight_format != LSK_WEIGHT_FORMAT_ELEM && weight_format != LSK_WEIGHT_FORMAT_FP8_E4M3 && weight_format != LSK_WEIGHT_FORMAT_MXFP4)
         return lsk_fail("lsk_engine_set_weight_format: unknown weight format %d", weight_format);
 #if LSK_ELEM_DTYPE != 0
-    if (weight_format != LSK_WEIGHT_FORMAT_ELEM) return lsk_fail("lsk_engine_set_weight_format: FP8 weight storage exists in the bf16 library only");
+    if (weight_format != LSK_WEIGHT_FORMAT_ELEM) return lsk_fail("lsk_engine_set_weight_format: FP8 / MXFP4 weight storage exists in the bf16 library only");
 #endif
     if (weight_format != e->weight_format) {                    // captured steps carry the kernel instances of the old format
         for (auto& g : e->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -267,6 +296,29 @@ extern "C" int lsk_engine_set_layer_prefill(lsk_engine* e, int32_t layer, const 
     if (bound != 0 && bound != 4) return lsk_fail("lsk_engine_set_layer_prefill: null weight (all four buffers, or four NULLs to unbind the layer's copies)");
     LayerWeights& lw = e->layers[layer];
     lw.pf_wqkv = (const elem_t*)wqkv; lw.pf_wo = (const elem_t*)wo; lw.pf_wgu = (const elem_t*)wgu; lw.pf_wdown = (const elem_t*)wdown;
+    return 0;
+}
+
+// bytes of the layer-sized scratch an MXFP4 engine prefills through: the four projections of one layer in the packed model-dtype layout
+static size_t prefill_scratch_bytes(const lsk_config& c, size_t (&off)[4]) {
+    const int qdim = c.n_heads * c.head_dim;
+    const size_t rows[4] = {(size_t)qdim + 2 * (size_t)c.n_kv_heads * c.head_dim, (size_t)c.hidden, 2 * (size_t)c.intermediate, (size_t)c.hidden};
+    const size_t ks[4] = {(size_t)c.hidden, (size_t)qdim, (size_t)c.hidden, (size_t)c.intermediate};
+    size_t at = 0;
+    for (int i = 0; i < 4; ++i) { off[i] = at; at += (rows[i] + 15) / 16 * 16 * ks[i] * sizeof(elem_t); }
+    return at;
+}
+
+extern "C" int lsk_engine_set_prefill_scratch(lsk_engine* e, void* scratch, size_t scratch_bytes) {
+#if LSK_ELEM_DTYPE != 0
+    if (scratch) return lsk_fail("lsk_engine_set_prefill_scratch: MXFP4 weight storage exists in the bf16 library only");
+#endif
+    if (!e) return lsk_fail("lsk_engine_set_prefill_scratch: null engine");
+    size_t off[4];
+    const size_t need = prefill_scratch_bytes(e->cfg, off);
+    if (scratch && scratch_bytes < need) return lsk_fail("lsk_engine_set_prefill_scratch: %zu bytes, a layer's four projections need %zu", scratch_bytes, need);
+    if (scratch && ((uintptr_t)scratch & 255)) return lsk_fail("lsk_engine_set_prefill_scratch: the scratch must be 256-byte aligned");
+    e->pf_scratch = (elem_t*)scratch;
     return 0;
 }
 
@@ -434,8 +486,10 @@ static int launch_attn(lsk_engine* e, const elem_t* q, elem_t* out, const elem_t
                               e->attn_part, e->n_pages, e->fused_attn ? e->attn_cnt : nullptr, st, ea, eb);
 }
 
-// bytes a projection launch streams: its packed weight (FP8 format: the codes and the rows' powers of two)
+// bytes a projection launch streams: its packed weight (FP8 format: the codes and the rows' powers of two; MXFP4: the codes and the
+// exponent table)
 static double gemm_stream_bytes(const GemmParams& p) {
+    if (p.wfmt == LSK_WF_MXFP4) return (double)p.wp_bytes + (double)p.n_tiles * 16 * lsk_mxfp4_ksp(p.K) + 16.0;
     return (double)p.wp_bytes + (p.wfmt == LSK_WF_FP8 ? (double)p.n_tiles * 16 * sizeof(float) : 0.0);
 }
 
@@ -484,7 +538,9 @@ int lsk_run_head_dev(lsk_engine* e, const elem_t* x, int m, float* logits, int l
     if (embed_dst != nullptr && !e->embed) return lsk_fail("the embedding is not bound on this engine");
     // sample=True (tokens_dev == nullptr): the logits rows are what the caller wants, nobody reads an argmax
     if (tokens_dev == nullptr && kv_add) return lsk_fail("internal: a head without an argmax launch cannot advance the context");
-    GemmLaunch<PRO_RMS, EPI_HEAD> g = gemm_head(e->cfg, x, m, e->lm_head, e->final_norm, logits, ld_logits, e->part_val, e->part_idx, e->weight_format);
+    // (the lm_head of an MXFP4 engine is stored in the FP8 format)
+    const int head_wf = e->weight_format == LSK_WEIGHT_FORMAT_MXFP4 ? LSK_WF_FP8 : e->weight_format;
+    GemmLaunch<PRO_RMS, EPI_HEAD> g = gemm_head(e->cfg, x, m, e->lm_head, e->final_norm, logits, ld_logits, e->part_val, e->part_idx, head_wf);
     hipEvent_t ea = nullptr, eb = nullptr;
     LSK_TRY(profile_pair(e, LSK_PROF_HEAD, m, gemm_stream_bytes(g.p), &ea, &eb));
     LSK_TRY(launch_head(g, LSK_HEAD_WGS > 0 ? LSK_HEAD_WGS : e->target_wgs, e->max_parts, tokens_dev, e->embed, embed_dst,
@@ -502,11 +558,37 @@ int lsk_embed_rows_dev(lsk_engine* e, const int* tokens_dev, int n, elem_t* dst,
 
 // What a layer's prefill launches read: the model-dtype copies of its dequantised projections where the caller bound them
 // (lsk_engine_set_layer_prefill: optional, FP8 weight format), read by the model-dtype instances; otherwise the buffers the decode
-// kernels read, in the engine's format (FP8: the FP8 instances read the codes)
+// kernels read, in the engine's format (FP8: the FP8 instances read the codes).  MXFP4 has no prefill instance: the layer's four
+// projections are widened on the stream into the engine's layer-sized scratch (lsk_engine_set_prefill_scratch, lsk_unpack_mxfp4_kernel)
+// -- exactly the bf16 values of the dequantised weights, in the packed model-dtype layout -- and the model-dtype instances read that.
 struct PrefillWeights { const elem_t *wqkv, *wo, *wgu, *wdown; int wfmt; };
-static PrefillWeights prefill_weights(const lsk_engine* e, const LayerWeights& lw) {
-    if (lw.pf_wqkv != nullptr) return {lw.pf_wqkv, lw.pf_wo, lw.pf_wgu, lw.pf_wdown, LSK_WF_ELEM};
-    return {lw.wqkv, lw.wo, lw.wgu, lw.wdown, e->weight_format == LSK_WEIGHT_FORMAT_FP8_E4M3 ? LSK_WF_FP8 : LSK_WF_ELEM};
+static int prefill_weights(const lsk_engine* e, const LayerWeights& lw, hipStream_t st, PrefillWeights* out) {
+    if (lw.pf_wqkv != nullptr) { *out = {lw.pf_wqkv, lw.pf_wo, lw.pf_wgu, lw.pf_wdown, LSK_WF_ELEM}; return 0; }
+    if (e->weight_format != LSK_WEIGHT_FORMAT_MXFP4) {
+        *out = {lw.wqkv, lw.wo, lw.wgu, lw.wdown, e->weight_format == LSK_WEIGHT_FORMAT_FP8_E4M3 ? LSK_WF_FP8 : LSK_WF_ELEM};
+        return 0;
+    }
+#if LSK_ELEM_DTYPE == 0
+    if (e->pf_scratch == nullptr) return lsk_fail("prefill of an MXFP4 engine needs its layer scratch (lsk_engine_set_prefill_scratch)");
+    const lsk_config& c = e->cfg;
+    const int qdim = c.n_heads * c.head_dim;
+    size_t off[4];
+    (void)prefill_scratch_bytes(c, off);
+    const elem_t* src[4] = {lw.wqkv, lw.wo, lw.wgu, lw.wdown};
+    const int rows[4] = {(qdim + 2 * c.n_kv_heads * c.head_dim + 15) / 16 * 16, (c.hidden + 15) / 16 * 16, (2 * c.intermediate + 15) / 16 * 16, (c.hidden + 15) / 16 * 16};
+    const int ks[4] = {c.hidden, qdim, c.hidden, c.intermediate};
+    elem_t* dst[4];
+    for (int i = 0; i < 4; ++i) {
+        dst[i] = (elem_t*)((unsigned char*)e->pf_scratch + off[i]);
+        const long long frags = (long long)(rows[i] / 16) * (ks[i] / 32) * 64;
+        hipLaunchKernelGGL(lsk_unpack_mxfp4_kernel, dim3((unsigned)((frags + 255) / 256)), dim3(256), 0, st, (const unsigned char*)src[i], rows[i], ks[i], dst[i]);
+        HIP_OK(hipGetLastError());
+    }
+    *out = {dst[0], dst[1], dst[2], dst[3], LSK_WF_ELEM};
+    return 0;
+#else
+    return lsk_fail("MXFP4 weight storage exists in the bf16 library only");
+#endif
 }
 
 // Prompt rows [0, n) of the bulk buffer through layers [lb, le) with the MFMA-tiled prefill kernels (lsk_launch_big.h).
@@ -516,7 +598,8 @@ static int run_bulk_big(lsk_engine* e, int n, int lb, int le, hipStream_t st) {
     const int* kvp = &e->state->kv_len;
     for (int l = lb; l < le; ++l) {
         const LayerWeights& lw = e->layers[l];
-        const PrefillWeights w = prefill_weights(e, lw);
+        PrefillWeights w;
+        LSK_TRY(prefill_weights(e, lw, st, &w));
         elem_t* kpool = e->kv_pool + (size_t)l * e->kv_layer_elems;
         elem_t* vpool = kpool + e->kv_half_elems;
         LSK_TRY(launch_rmsnorm_rows(c, e->hbulk, n, lw.norm1, e->xn_bulk, st));

@@ -49,8 +49,8 @@ struct UnitInfo {
     int steps_c;     // k-steps of the chunk
 };
 
-// WB: bytes per packed weight element (LSK_EB in the model-dtype format, 1 in the FP8 format)
-template <int NW, int WB = LSK_EB>
+// FB: bytes of a lane's 8-element fragment in the packed weight (8 LSK_EB in the model-dtype format, 8 in the FP8 format, 4 in MXFP4)
+template <int NW, int FB = 8 * LSK_EB>
 __device__ __forceinline__ UnitInfo lsk_unit_info(int u, int units, int ntl, int ksteps, int tile0, int w, int lane) {
     constexpr int WAVES = NW, KC_STEPS = NW * LSK_SPW;
     UnitInfo r;
@@ -62,7 +62,7 @@ __device__ __forceinline__ UnitInfo lsk_unit_info(int u, int units, int ntl, int
     const int ks0 = w * spw;
     r.c = c; r.tl = tl; r.ks0 = ks0; r.steps_c = steps_c;
     r.nvalid = max(0, min(spw, steps_c - ks0));
-    r.off0 = ((unsigned)(tile0 + tl) * (unsigned)ksteps + (unsigned)(c * KC_STEPS + ks0)) * (unsigned)(512 * WB) + (unsigned)lane * (unsigned)(8 * WB);
+    r.off0 = ((unsigned)(tile0 + tl) * (unsigned)ksteps + (unsigned)(c * KC_STEPS + ks0)) * (unsigned)(64 * FB) + (unsigned)lane * (unsigned)FB;
     return r;
 }
 
@@ -97,18 +97,47 @@ __device__ __forceinline__ elem8 lsk_ring_frag(const u32x4 (&ring)[LSK_SPW * LSK
 // are widened to bf16 at consumption (exact: 3 mantissa bits into 7) and go through the SAME MFMA in the SAME order as the bf16 format;
 // the row's power of two multiplies the reduced fp32 tile once, in front of the epilogue's first rounding.  A power of two commutes
 // with every fp32 rounding of the accumulation, so the result is bit for bit the bf16 kernel's on the dequantised weights.
-enum { LSK_WF_ELEM = 0, LSK_WF_FP8 = 1 };
+//
+// LSK_WF_MXFP4 (bf16 build only, opt-in; q/k/v, o_proj, gate/up and down -- the lm_head of such an engine stays FP8): OCP MXFP4, e2m1
+// codes with one E8M0 exponent byte per block of 32 consecutive input features of a row (= one k-step of a row), same tile order.  A
+// k-step of a tile is 256 B, a lane's fragment 4 B (its eight codes, element i in the nibble v_cvt_scalef32_pk_bf16_fp4 reads for
+// sel = i / 2: low nibble first), one raw_buffer_load_b32 per ring slot.  Behind the codes sits the exponent table: one byte per
+// (packed row, k-step), row-major with a row stride of ceil(K / 128) * 4 bytes (lsk_mxfp4_ksp; +16 bytes at the very end), so the
+// exponents of a lane's row for the <= 16 consecutive k-steps its wave owns in a unit are 16 consecutive bytes.  A wave's first k-step
+// is not a multiple of 4 in ragged chunks (K = 11 008: 11 or 6 k-steps per wave), so a lane fetches the DWORD-ALIGNED 20-byte window around
+// them -- one 16-byte and one 4-byte load per unit, requested one unit ahead, from clamped always-valid addresses (the row stride's
+// padding and the 16 bytes behind the table are what the window of the last k-steps of the last row reaches) -- and a wave-uniform
+// funnel shift puts step s in byte s.  At consumption a slot's eight codes become eight bf16 with four v_cvt_scalef32_pk_bf16_fp4 (the
+// block's 2^e = byte << 23 as the fp32 scale: code * 2^e is exact in bf16, nothing rounds), and go through the SAME MFMA in the SAME
+// order; there is no multiply behind the accumulation.  The sums are the bf16 kernel's on the dequantised weights, term for term.
+// Every byte of the table is an exponent in [2, 251] or the padding's 127, so the zeros the bounds check returns for the slots beyond
+// a wave's share stay zeros whatever byte their window position holds.
+enum { LSK_WF_ELEM = 0, LSK_WF_FP8 = 1, LSK_WF_MXFP4 = 2 };
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-template <int WF> struct lsk_wfmt { typedef u32x4 slot_t; static constexpr int SLOTS = LSK_SPW * LSK_LPF, WB = LSK_EB; };
-template <> struct lsk_wfmt<LSK_WF_FP8> { typedef u32x2 slot_t; static constexpr int SLOTS = LSK_SPW, WB = 1; };
+template <int WF> struct lsk_wfmt { typedef u32x4 slot_t; static constexpr int SLOTS = LSK_SPW * LSK_LPF, FB = 8 * LSK_EB; };
+template <> struct lsk_wfmt<LSK_WF_FP8> { typedef u32x2 slot_t; static constexpr int SLOTS = LSK_SPW, FB = 8; };
+template <> struct lsk_wfmt<LSK_WF_MXFP4> { typedef unsigned slot_t; static constexpr int SLOTS = LSK_SPW, FB = 4; };
+// bytes between the rows of the MXFP4 exponent table: the k-steps rounded up to whole dwords
+__host__ __device__ inline int lsk_mxfp4_ksp(int K) { return ((K >> 5) + 3) & ~3; }
+// bytes of the packed weight of n_tiles tiles in format wfmt that the ring streams (the tiles; FP8 / MXFP4: the scale table follows them)
+__host__ inline size_t lsk_wf_tile_bytes(int wfmt, int n_tiles, int K) {
+    const size_t elems = (size_t)n_tiles * 16 * (size_t)K;
+    return wfmt == LSK_WF_MXFP4 ? elems / 2 : (wfmt == LSK_WF_FP8 ? elems : elems * sizeof(elem_t));
+}
 
 #define lsk_ring_fill_fp8(ring, s, rsrc, u, valid) do { \
         const unsigned lsk_off = (valid) ? (u).off0 + (unsigned)(s) * 512u : LSK_OOB_OFFSET; \
         (ring)[s] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, lsk_off, 0, 2 /* nt */); \
     } while (0)
+#define lsk_ring_fill_mxfp4(ring, s, rsrc, u, valid) do { \
+        const unsigned lsk_off = (valid) ? (u).off0 + (unsigned)(s) * 256u : LSK_OOB_OFFSET; \
+        (ring)[s] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, lsk_off, 0, 2 /* nt */); \
+    } while (0)
 // (inside a template on WF: the branch not taken is never instantiated, so each form only sees its own slot type)
 #define lsk_ring_fill_wf(WF, ring, s, rsrc, u, valid) do { \
-        if constexpr ((WF) == LSK_WF_FP8) lsk_ring_fill_fp8(ring, s, rsrc, u, valid); else lsk_ring_fill(ring, s, rsrc, u, valid); \
+        if constexpr ((WF) == LSK_WF_FP8) lsk_ring_fill_fp8(ring, s, rsrc, u, valid); \
+        else if constexpr ((WF) == LSK_WF_MXFP4) lsk_ring_fill_mxfp4(ring, s, rsrc, u, valid); \
+        else lsk_ring_fill(ring, s, rsrc, u, valid); \
     } while (0)
 #if LSK_ELEM_DTYPE == 0
 // 8 e4m3 codes -> 8 bf16: v_cvt_pk_f32_fp8 (OCP on gfx950) gives two fp32 whose low 16 bits are zero, so the bf16 is the high half --
@@ -126,6 +155,40 @@ __device__ __forceinline__ elem8 lsk_ring_frag(const u32x2 (&ring)[LSK_SPW], int
     o[0] = lsk_fp8x2_to_bf16x2(c[0], false); o[1] = lsk_fp8x2_to_bf16x2(c[0], true);
     o[2] = lsk_fp8x2_to_bf16x2(c[1], false); o[3] = lsk_fp8x2_to_bf16x2(c[1], true);
     return __builtin_bit_cast(elem8, o);
+}
+// 8 e2m1 codes (a lane's 4-byte MXFP4 fragment) x 2^e -> 8 bf16: byte i of the dword holds elements 2 i (low nibble) and 2 i + 1
+typedef __bf16 lsk_bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ elem8 lsk_mxfp4_frag(unsigned codes, float scale) {
+    u32x4 o;
+    o[0] = __builtin_bit_cast(unsigned, (lsk_bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 0));
+    o[1] = __builtin_bit_cast(unsigned, (lsk_bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 1));
+    o[2] = __builtin_bit_cast(unsigned, (lsk_bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 2));
+    o[3] = __builtin_bit_cast(unsigned, (lsk_bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 3));
+    return __builtin_bit_cast(elem8, o);
+}
+// The exponent bytes of a lane's row for the k-steps of one unit: the dword-aligned 20-byte window (lsk_mxfp4_window_load), then the bytes of
+// steps 0..15 in order (lsk_mxfp4_window_align: `sh` = 8 x (first k-step mod 4), wave-uniform), then step s's 2^e as fp32.
+typedef u32x4 lsk_u32x4_a4 __attribute__((aligned(4)));       // a 16-byte load from a dword-aligned address
+struct lsk_mx_window { u32x4 lo; unsigned hi; };
+__device__ __forceinline__ lsk_mx_window lsk_mxfp4_window_load(const unsigned char* table, int ksp, int ksteps, int row, const UnitInfo& u, int kc_steps) {
+    const int ks = min(u.c * kc_steps + u.ks0, ksteps - 1);      // (a wave without a share of the chunk: any valid window)
+    const unsigned char* p = table + (size_t)row * ksp + (ks & ~3);
+    lsk_mx_window r;
+    r.lo = *(const lsk_u32x4_a4*)p;                               // (the row stride and ks & ~3 are multiples of 4, not of 16)
+    r.hi = *(const unsigned*)(p + 16);
+    return r;
+}
+__device__ __forceinline__ u32x4 lsk_mxfp4_window_align(const lsk_mx_window& r, const UnitInfo& u, int ksteps, int kc_steps) {
+    const int sh = (min(u.c * kc_steps + u.ks0, ksteps - 1) & 3) * 8;
+    u32x4 o;
+    o[0] = (unsigned)((((unsigned long long)r.lo[1] << 32) | r.lo[0]) >> sh);
+    o[1] = (unsigned)((((unsigned long long)r.lo[2] << 32) | r.lo[1]) >> sh);
+    o[2] = (unsigned)((((unsigned long long)r.lo[3] << 32) | r.lo[2]) >> sh);
+    o[3] = (unsigned)((((unsigned long long)r.hi << 32) | r.lo[3]) >> sh);
+    return o;
+}
+__device__ __forceinline__ float lsk_mxfp4_scale(const u32x4& sc, int s) {
+    return __builtin_bit_cast(float, ((sc[s >> 2] >> (8 * (s & 3))) & 0xffu) << 23);
 }
 #endif
 
@@ -316,13 +379,26 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
     }
 
     // ---- activations next (they must not queue behind the weight ring), then fill the ring ----
-    UnitInfo cur = lsk_unit_info<NW, lsk_wfmt<WF>::WB>(0, units, ntl, ksteps, tile0, w, lane);
+    UnitInfo cur = lsk_unit_info<NW, lsk_wfmt<WF>::FB>(0, units, ntl, ksteps, tile0, w, lane);
+    // MXFP4 weights: the exponent bytes of this lane's row for the wave's k-steps of the first unit (addresses from preloaded arguments
+    // only: out in front of the rows and the ring); mxs: the current unit's bytes in step order, mxn: the next unit's window in flight
+    [[maybe_unused]] u32x4 mxs;
+    [[maybe_unused]] const unsigned char* mxtab = nullptr;
+    [[maybe_unused]] int mxksp = 0;
+#if LSK_ELEM_DTYPE == 0
+    [[maybe_unused]] lsk_mx_window mxn;
+    if constexpr (WF == LSK_WF_MXFP4) {
+        mxtab = (const unsigned char*)hp.wp + hp.wp_bytes;
+        mxksp = lsk_mxfp4_ksp(hp.K);
+        mxn = lsk_mxfp4_window_load(mxtab, mxksp, ksteps, (tile0 + cur.tl) * 16 + c16, cur, KC_STEPS);
+    }
+#endif
     LSK_TRACE_POINT(9);                                           // address arithmetic done, nothing requested yet
     elem8 xr[MB];
     elem8 nw = {};
     float ss[MB];
     float sv[MB];                 // per-row 1/rms (PRO_RMS), wave-uniform
-    typename lsk_wfmt<WF>::slot_t ring[lsk_wfmt<WF>::SLOTS];      // fp32: two 16-byte halves per fragment (lsk_ring_fill); FP8 weights: 8-byte slots
+    typename lsk_wfmt<WF>::slot_t ring[lsk_wfmt<WF>::SLOTS];      // fp32: two 16-byte halves per fragment (lsk_ring_fill); FP8 weights: 8-byte slots, MXFP4: 4-byte slots
     // Multi-row RMSNorm launches of a one-chunk K (the verify pass's q/k/v, gate/up and lm_head at hidden <= 4096): the normalisation
     // of 8 rows is ~450 VALU instructions per thread, ~2 us for the CU whoever executes them, and it used to start only when the LAST
     // wave was through the throttled issue of its ring (4.4 us: requests leave a CU at the HBM rate) -- a hole in the stream, rows staged
@@ -469,52 +545,27 @@ __device__ __forceinline__ void lsk_gemm_body(const GemmHot& hp, const GemmParam
     elem8 afr[LSK_SPW];
 #pragma unroll
     for (int s = 0; s < LSK_SPW; ++s) afr[s] = *(const elem8*)(xa + min(cur.ks0 + s, cur.steps_c - 1) * (32 * LSK_EB));
-
-    for (int u = 0; u < units; ++u) {
-        const UnitInfo nxt = lsk_unit_info<NW, lsk_wfmt<WF>::WB>(u + 1, units, ntl, ksteps, tile0, w, lane);
-        if (nchunks > 1 && cur.tl == 0 && u > 0) {
-            // every wave passed the previous unit's barrier => nobody still reads the old chunk; the rows
-            // of this chunk were prefetched into xr one chunk ago, the next chunk's are requested now
-            lsk_store_chunk<PRO, MB>(hp, xs, xstride, sv, cur.steps_c, tid, xr, nw);
-            if (cur.c + 1 < nchunks)
-                lsk_load_chunk<PRO, MB, NW>(hp, cur.c + 1, min(KC_STEPS, ksteps - (cur.c + 1) * KC_STEPS), tid, xr, nw);
-            __syncthreads();
-#pragma unroll
-            for (int s = 0; s < LSK_SPW; ++s) afr[s] = *(const elem8*)(xa + min(cur.ks0 + s, cur.steps_c - 1) * (32 * LSK_EB));
-        }
-        [[maybe_unused]] float scn;
-        if constexpr (WF == LSK_WF_FP8 && EPI == EPI_HEAD)      // (an exhausted `nxt` names tile 0 of the workgroup: valid, unused)
-            scn = ((const float*)((const unsigned char*)hp.wp + hp.wp_bytes))[(tile0 + nxt.tl) * 16 + c16];
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < LSK_SPW; ++s) {
-            acc = LSK_MFMA_16x16x32(afr[s], lsk_ring_frag(ring, s), acc, 0, 0, 0);
-#ifdef LSK_TRACE
-            if (u == 0 && s == 0) LSK_TRACE_POINT(3);             // first weight fragment arrived
-            if (u == 0 && s == LSK_SPW - 1) LSK_TRACE_POINT(4);   // first unit's fragments all arrived
+#if LSK_ELEM_DTYPE == 0
+    if constexpr (WF == LSK_WF_MXFP4) mxs = lsk_mxfp4_window_align(mxn, cur, ksteps, KC_STEPS);
 #endif
-            lsk_ring_fill_wf(WF, ring, s, rsrc, nxt, s < nxt.nvalid);
-            // (hipcc sinks these refills into bursts behind later MFMAs, so the ring runs ~8-16 deep; pinning
-            //  "consume s -> refill s" with sched_barrier(0) gives the textbook vmcnt(15) stream but measured
-            //  0..-4 % on every shape -- the HBM pipe is already full at ~8 KiB per wave in flight)
+
+    // The first unit never crosses a chunk boundary.  hipcc peels it off the loop of the bf16-format instances with up to 10 row
+    // slots and of every residual launch (their `u > 0` test then folds away); the MXFP4 loop is longer by the converts and stays
+    // whole under the same heuristic, so there the first unit is peeled by hand where the bf16 twin's is: twin and MXFP4 instance keep
+    // the same shape (tests/test_mxfp4_format.py compares them).  Every other instance is the loop it always was.
+    constexpr bool kPeelFirstUnit = WF == LSK_WF_MXFP4 && !(PRO == PRO_RMS && MB > 10);
+    if constexpr (kPeelFirstUnit) {
+        {
+            const int u = 0;                                      // (units >= 1: a workgroup owns at least one tile)
+#include "lsk_gemm_unit.h"
         }
-        float* sl = slab + ((u & 1) * WAVES + w) * 256;
-        *(f32x4*)(sl + lane * 4) = acc;
-        __syncthreads();
-        const int owner = (EPI == EPI_SWIGLU) ? (cur.tl >> 1) : (EPI == EPI_HEAD ? (cur.tl & (WAVES - 1)) : cur.tl);
-        if (w == owner) {
-            const float* sb = slab + (u & 1) * WAVES * 256 + lane * 4;
-            f32x4 t = *(const f32x4*)sb;
-#pragma unroll
-            for (int ww = 1; ww < WAVES; ++ww) t += *(const f32x4*)(sb + ww * 256);
-            if (EPI == EPI_HEAD && nchunks == 1) {
-                if constexpr (WF == LSK_WF_FP8) t *= scu;
-                lsk_head_tile(p, t, (tile0 + cur.tl) * 16 + c16, hp.N, M, rg, rbv, rbi);
-            } else if (EPI == EPI_SWIGLU && (cur.tl & 1)) own1 += t;
-            else own0 += t;
+        for (int u = 1; u < units; ++u) {
+#include "lsk_gemm_unit.h"
         }
-        if constexpr (WF == LSK_WF_FP8 && EPI == EPI_HEAD) scu = scn;
-        cur = nxt;
+    } else {
+        for (int u = 0; u < units; ++u) {
+#include "lsk_gemm_unit.h"
+        }
     }
     LSK_TRACE_POINT(5);                                           // last unit reduced
     // FP8 weights: the rows' powers of two, once, on the reduced fp32 sums and in front of every rounding below

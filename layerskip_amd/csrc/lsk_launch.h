@@ -41,6 +41,11 @@ constexpr bool lsk_has_fp8() { return LSK_ELEM_DTYPE == 0 && EPI != EPI_F32; }
 template <int PRO, int EPI>
 constexpr bool lsk_has_fp8_8w() { return lsk_has_fp8<EPI>() && PRO == PRO_RMS && EPI != EPI_HEAD; }
 
+// The MXFP4 weight format (lsk_gemm.h): the bf16 build's q/k/v, o_proj, gate/up and down launches, with the FP8 format's wave counts.
+// No lm_head instance: the head of an MXFP4 engine is stored and launched in the FP8 format.
+template <int EPI>
+constexpr bool lsk_has_mxfp4() { return lsk_has_fp8<EPI>() && EPI != EPI_HEAD; }
+
 template <int PRO, int EPI, int NW, int WF>
 static int set_gemm_attr_nw() {
     HIP_OK(hipFuncSetAttribute((const void*)lsk_gemm_kernel<PRO, EPI, 1, NW, WF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxGemmLds));
@@ -60,6 +65,10 @@ static int set_gemm_attr() {
     if constexpr (lsk_has_fp8<EPI>()) {
         LSK_TRY((set_gemm_attr_nw<PRO, EPI, 4, LSK_WF_FP8>()));
         if constexpr (lsk_has_fp8_8w<PRO, EPI>()) LSK_TRY((set_gemm_attr_nw<PRO, EPI, 8, LSK_WF_FP8>()));
+    }
+    if constexpr (lsk_has_mxfp4<EPI>()) {
+        LSK_TRY((set_gemm_attr_nw<PRO, EPI, 4, LSK_WF_MXFP4>()));
+        if constexpr (lsk_has_fp8_8w<PRO, EPI>()) LSK_TRY((set_gemm_attr_nw<PRO, EPI, 8, LSK_WF_MXFP4>()));
     }
     return 0;
 }
@@ -128,7 +137,7 @@ static int launch_gemm_nw(GemmParams& p, int target_wgs, hipStream_t st, int* gr
     if (p.n_tiles != (p.N + 15) / 16) return lsk_fail("gemm: n_tiles %d is not ceil(N / 16) of N = %d", p.n_tiles, p.N);   // the kernel derives it
     if (lds > kMaxGemmLds) return lsk_fail("gemm LDS %zu exceeds %zu", lds, kMaxGemmLds);
     // 32-bit buffer offsets; the out-of-range sentinel of ragged ring slots must stay beyond the descriptor's range
-    if ((size_t)p.n_tiles * 16 * (size_t)p.K * (size_t)lsk_wfmt<WF>::WB >= (size_t)LSK_OOB_OFFSET) return lsk_fail("packed weight of %d x %d exceeds the 32-bit buffer range", p.n_tiles * 16, p.K);
+    if (lsk_wf_tile_bytes(WF, p.n_tiles, p.K) >= (size_t)LSK_OOB_OFFSET) return lsk_fail("packed weight of %d x %d exceeds the 32-bit buffer range", p.n_tiles * 16, p.K);
 #ifdef LSK_TRACE
     p.trace = lsk_trace_next(0, (PRO * 16 + EPI) | (p.K << 8), p.M, grid);
 #endif
@@ -150,6 +159,15 @@ static int launch_gemm(GemmParams& p, int target_wgs, hipStream_t st, int* grid_
     if (p.wfmt != LSK_WF_ELEM) {
         // the same lsk_gemm_waves rule as the bf16 format: the summation order of an output element is the bf16 kernel's
         if constexpr (lsk_has_fp8<EPI>()) {
+            if (p.wfmt == LSK_WF_MXFP4) {
+                if constexpr (lsk_has_mxfp4<EPI>()) {
+                    if (lsk_gemm_waves(PRO, EPI, p.K) == 4) return launch_gemm_nw<PRO, EPI, 4, LSK_WF_MXFP4>(p, target_wgs, st, grid_out, ev_start, ev_stop);
+                    if constexpr (lsk_has_fp8_8w<PRO, EPI>()) return launch_gemm_nw<PRO, EPI, 8, LSK_WF_MXFP4>(p, target_wgs, st, grid_out, ev_start, ev_stop);
+                    else return lsk_fail("gemm: no eight-wave MXFP4 form of this projection (LSK_FORCE_WAVES measurement builds: bf16 format only)");
+                } else {
+                    return lsk_fail("gemm: the lm_head has no MXFP4 kernel (an MXFP4 engine's head is FP8)");
+                }
+            }
             if (p.wfmt != LSK_WF_FP8) return lsk_fail("gemm: unknown weight format %d", p.wfmt);
             if (lsk_gemm_waves(PRO, EPI, p.K) == 4) return launch_gemm_nw<PRO, EPI, 4, LSK_WF_FP8>(p, target_wgs, st, grid_out, ev_start, ev_stop);
             if constexpr (lsk_has_fp8_8w<PRO, EPI>()) return launch_gemm_nw<PRO, EPI, 8, LSK_WF_FP8>(p, target_wgs, st, grid_out, ev_start, ev_stop);
@@ -178,11 +196,11 @@ struct GemmLaunch {
 };
 
 // m rows of x ([m][K]) against the packed weight of N output features
-// (wfmt: the format of wp -- LSK_WF_ELEM, or LSK_WF_FP8: 1-byte codes, wp_bytes counts them)
+// (wfmt: the format of wp -- LSK_WF_ELEM, LSK_WF_FP8: 1-byte codes, or LSK_WF_MXFP4: 4-bit codes; wp_bytes counts the tiles alone)
 static GemmParams gemm_params(const elem_t* x, int m, int K, const elem_t* wp, int N, int wfmt = LSK_WF_ELEM) {
     GemmParams p{};
     p.x = x; p.ldx = K; p.M = m; p.K = K; p.N = N; p.n_tiles = (N + 15) / 16;
-    p.wp = wp; p.wp_bytes = (unsigned)((size_t)p.n_tiles * 16 * K * (wfmt == LSK_WF_FP8 ? 1 : sizeof(elem_t)));
+    p.wp = wp; p.wp_bytes = (unsigned)lsk_wf_tile_bytes(wfmt, p.n_tiles, K);
     p.wfmt = wfmt;
     return p;
 }

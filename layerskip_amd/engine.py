@@ -104,6 +104,8 @@ class HipEngine:
         # weight_format="fp8_e4m3" (opt-in; "bf16" = the model dtype, the default): the projections are stored as e4m3 codes with one
         # power of two per output row (layerskip_amd/quant.py) and the decode path streams half the bytes; bit-identical to this engine
         # in bf16 on quant.dequantized_model(model).  The bf16 library only.
+        # weight_format="mxfp4" (opt-in): q/k/v/o/gate/up/down as OCP MXFP4 (e2m1 codes, one power of two per 32-feature block), the
+        # lm_head in the FP8 format; bit-identical to this engine in bf16 on quant.dequantized_model(model, "mxfp4").
         if weight_format != "bf16" and dtype_name != "bf16":
             raise _lib.LskError(f"weight_format={weight_format!r} needs a bf16 model; this one is {dtype_name} "
                                 "(FP8 weight storage exists in the bf16 build only)")
@@ -111,7 +113,9 @@ class HipEngine:
         # what the MFMA-tiled prefill kernels read under FP8: the same codes as the decode kernels (their FP8 instances widen them in
         # the weight ring and scale the accumulators, csrc/lsk_gemm_big.h), so prompt KV and exit hiddens are the bf16 engine's on the
         # dequantised model and packed bytes are 0.5 x bf16's.  None in the default format.  One set of buffers serves both paths.
-        self.prefill_weights = "fp8_codes" if weight_format == "fp8_e4m3" else None
+        # Under MXFP4 no prefill kernel reads the codes: the engine widens one layer at a time into a layer-sized bf16 scratch
+        # (_allocate) and the model-dtype prefill kernels read that.
+        self.prefill_weights = {"fp8_e4m3": "fp8_codes", "mxfp4": "mxfp4_layer_scratch"}.get(weight_format)
         self.lib = _lib.load(dtype=dtype_name)
         self.elem_bytes = torch.empty(0, dtype=self.dtype).element_size()
         # sample=True on the device: the sampler's 16-bit logit keys are exact at bf16 / fp16 only (lsk_key16, lsk_sample.h).  Over fp32
@@ -225,29 +229,37 @@ class HipEngine:
     def _fp8(self) -> bool:
         return self.weight_format == "fp8_e4m3"
 
-    def _packed_buffer(self, n_rows: int, k: int, fp8: bool):
-        """The packed buffer of an [n_rows][k] projection (FP8: the codes, then one fp32 power of two per packed row)."""
+    @property
+    def _head_format(self) -> str:
+        """The format of the packed lm_head: the engine's, except that an MXFP4 engine keeps its head in the FP8 format."""
+        return "fp8_e4m3" if self.weight_format == "mxfp4" else self.weight_format
+
+    def _packed_buffer(self, n_rows: int, k: int, fmt: str):
+        """The packed buffer of an [n_rows][k] projection in format `fmt` (FP8: the codes, then one fp32 power of two per packed row;
+        MXFP4: the codes, then the blocks' exponent bytes)."""
         nbytes = ctypes.c_size_t(0)
-        self._ck((self.lib.lsk_packed_bytes_fp8 if fp8 else self.lib.lsk_packed_bytes)(n_rows, k, ctypes.byref(nbytes)))
+        fn = {"bf16": self.lib.lsk_packed_bytes, "fp8_e4m3": self.lib.lsk_packed_bytes_fp8, "mxfp4": self.lib.lsk_packed_bytes_mxfp4}[fmt]
+        self._ck(fn(n_rows, k, ctypes.byref(nbytes)))
         return torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
 
-    def _pack_into(self, dst, w: torch.Tensor, tile_offset: int, tile_stride: int, rope_hd: int, fp8: bool) -> None:
+    def _pack_into(self, dst, w: torch.Tensor, tile_offset: int, tile_stride: int, rope_hd: int, fmt: str, dst_rows: int = 0) -> None:
+        """`dst_rows`: the rows of the whole destination (a multiple of 16), which locate the scale table of the quantised formats."""
         w = w.detach()
         if w.dtype != self.dtype or w.device != self.device:
             raise _lib.LskError(f"all projection weights must be {self.dtype} on the engine's device")
         if w.stride(1) != 1:
             w = w.contiguous()
-        if not fp8:
+        if fmt == "bf16":
             self._ck(self.lib.lsk_pack_linear(w.data_ptr(), w.shape[0], w.shape[1], w.stride(0), dst.data_ptr(),
                                            tile_offset, tile_stride, rope_hd, self._stream))
             return
-        rows = dst.numel() // (w.shape[1] + 4)       # packed rows of the destination: they locate its scale table
-        self._ck(self.lib.lsk_pack_linear_fp8(w.data_ptr(), w.shape[0], w.shape[1], w.stride(0), dst.data_ptr(), rows,
-                                           tile_offset, tile_stride, rope_hd, self._stream))
+        fn = self.lib.lsk_pack_linear_fp8 if fmt == "fp8_e4m3" else self.lib.lsk_pack_linear_mxfp4
+        self._ck(fn(w.data_ptr(), w.shape[0], w.shape[1], w.stride(0), dst.data_ptr(), dst_rows, tile_offset, tile_stride, rope_hd,
+                    self._stream))
 
-    def _pack_projections(self, layer, fp8: bool, values=lambda w: w):
-        """(wqkv, wo, wgu, wdown) of one decoder layer, packed: q|k|v concatenated (q and k in RoPE row order), gate / up interleaved by
-        tile.  `values` maps a weight to what is packed in its place."""
+    def _pack_projections(self, layer, fmt: str, values=lambda w: w):
+        """(wqkv, wo, wgu, wdown) of one decoder layer, packed in format `fmt`: q|k|v concatenated (q and k in RoPE row order), gate / up
+        interleaved by tile.  `values` maps a weight to what is packed in its place.  Nothing here synchronises."""
         hd, H, I = self.head_dim, self.hidden, self.intermediate
         qdim, kvdim = self.n_heads * hd, self.n_kv_heads * hd
         a, mlp = layer.self_attn, layer.mlp
@@ -257,28 +269,33 @@ class HipEngine:
                 (H, I, ((mlp.down_proj, 0, 1, 0),)))
         out = []
         for n_rows, k, parts in plan:
-            buf = self._packed_buffer(n_rows, k, fp8)
+            buf = self._packed_buffer(n_rows, k, fmt)
             for lin, tile_offset, tile_stride, rope_hd in parts:
-                self._pack_into(buf, values(lin.weight), tile_offset, tile_stride, rope_hd, fp8)
+                self._pack_into(buf, values(lin.weight), tile_offset, tile_stride, rope_hd, fmt, _round_up(n_rows, 16))
             out.append(buf)
         return tuple(out)
 
     def packed_weight_bytes(self) -> dict:
         """Bytes of the packed projection buffers (this engine's layers and its lm_head): "decode" -- the buffers the decode path reads,
-        which in either weight format are the ones prefill reads too; "prefill_only" -- buffers that only the prefill kernels read (0)."""
+        which in the bf16 and FP8 formats are the ones prefill reads too; "prefill_only" -- buffers that only the prefill kernels read
+        (0); and, on an MXFP4 engine only, "prefill_scratch" -- the layer-sized bf16 scratch it widens one layer at a time into."""
         bufs = [t for pk in self._packed if pk is not None for t in pk[:4]]
         bufs += [self._globals["lm_head"]] if self._globals.get("lm_head") is not None else []
-        return {"decode": sum(t.numel() for t in bufs),
-                "prefill_only": sum(t.numel() for pk in self._packed_prefill.values() for t in pk)}
+        out = {"decode": sum(t.numel() for t in bufs),
+               "prefill_only": sum(t.numel() for pk in self._packed_prefill.values() for t in pk)}
+        if self._buffers.get("prefill_scratch") is not None:
+            out["prefill_scratch"] = self._buffers["prefill_scratch"].numel()
+        return out
 
     def _bind_prefill_copies(self, layers=None, bind: bool = True) -> None:
-        """A/B lever of tools/ and tests/, FP8 engines only: bf16-packed copies of the DEQUANTISED projections of `layers` (default: all of
+        """A/B lever of tools/ and tests/, FP8 and MXFP4 engines only: bf16-packed copies of the DEQUANTISED projections of `layers` (default: all of
         this engine's), bound with lsk_engine_set_layer_prefill, so that those layers prefill through the model-dtype kernels -- what
         every FP8 engine did before the prefill kernel read the codes.  bind=False unbinds and frees them."""
         from . import quant
         for i in (range(*self.layer_range) if layers is None else layers):
             if bind:
-                self._packed_prefill[i] = self._pack_projections(self.model.model.layers[i], False, quant.dequantize_weight)
+                self._packed_prefill[i] = self._pack_projections(self.model.model.layers[i], "bf16",
+                                                                 lambda w: quant.dequantize_weight(w, self.weight_format))
                 torch.cuda.synchronize(self.device)          # the dequantised values are temporaries: the pack kernels must be through
                 ptrs = [t.data_ptr() for t in self._packed_prefill[i]]
             else:
@@ -289,14 +306,24 @@ class HipEngine:
     def unpacked_fp8(self, layer: int, name: str):
         """(codes uint8 [rows][k], scale fp32 [rows]) of a packed FP8 buffer in PACKED row order (quant.unpack_tiles); name: wqkv | wo |
         wgu | wdown | lm_head."""
-        if not self._fp8:
-            raise _lib.LskError("unpacked_fp8: this engine stores its weights in the model dtype")
+        if not (self._fp8 or (self.weight_format == "mxfp4" and name == "lm_head")):
+            raise _lib.LskError("unpacked_fp8: this buffer of the engine is not stored as FP8")
         from . import quant
         hd, H, I = self.head_dim, self.hidden, self.intermediate
         shapes = {"wqkv": ((self.n_heads + 2 * self.n_kv_heads) * hd, H), "wo": (H, self.n_heads * hd), "wgu": (2 * I, H),
                   "wdown": (H, I), "lm_head": (self.vocab, H)}
         buf = self._globals["lm_head"] if name == "lm_head" else self._packed[layer][("wqkv", "wo", "wgu", "wdown").index(name)]
         return quant.unpack_tiles(buf, *shapes[name])
+
+    def unpacked_mxfp4(self, layer: int, name: str):
+        """(codes uint8 [rows][k/2], exp uint8 [rows][k/32]) of a packed MXFP4 buffer in PACKED row order (quant.unpack_tiles_mxfp4);
+        name: wqkv | wo | wgu | wdown (the lm_head of an MXFP4 engine is FP8: unpacked_fp8)."""
+        if self.weight_format != "mxfp4":
+            raise _lib.LskError("unpacked_mxfp4: this engine does not store its weights as MXFP4")
+        from . import quant
+        hd, H, I = self.head_dim, self.hidden, self.intermediate
+        shapes = {"wqkv": ((self.n_heads + 2 * self.n_kv_heads) * hd, H), "wo": (H, self.n_heads * hd), "wgu": (2 * I, H), "wdown": (H, I)}
+        return quant.unpack_tiles_mxfp4(self._packed[layer][("wqkv", "wo", "wgu", "wdown").index(name)], *shapes[name])
 
     def _pack_weights(self, m) -> None:
         H = self.hidden
@@ -307,7 +334,7 @@ class HipEngine:
             a, mlp = layer.self_attn, layer.mlp
             n1 = layer.input_layernorm.weight.detach().contiguous()
             n2 = layer.post_attention_layernorm.weight.detach().contiguous()
-            self._packed.append(self._pack_projections(layer, self._fp8) + (n1, n2))
+            self._packed.append(self._pack_projections(layer, self.weight_format) + (n1, n2))
             if self.release_weights:
                 torch.cuda.synchronize(self.device)
                 for lin in (a.q_proj, a.k_proj, a.v_proj, a.o_proj, mlp.gate_proj, mlp.up_proj, mlp.down_proj):
@@ -317,8 +344,8 @@ class HipEngine:
         have_head, have_embed = not m.lm_head.weight.is_meta, not m.model.embed_tokens.weight.is_meta
         self._globals["lm_head"] = None
         if have_head:
-            head = self._packed_buffer(self.vocab, H, self._fp8)
-            self._pack_into(head, m.lm_head.weight, 0, 1, 0, self._fp8)
+            head = self._packed_buffer(self.vocab, H, self._head_format)
+            self._pack_into(head, m.lm_head.weight, 0, 1, 0, self._head_format, _round_up(self.vocab, 16))
             self._globals["lm_head"] = head
             tied = have_embed and m.lm_head.weight.data_ptr() == m.model.embed_tokens.weight.data_ptr()
             if self.release_weights and not tied:
@@ -354,6 +381,17 @@ class HipEngine:
         self._buffers.pop("sampling", None)
         self._buffers["ws"] = torch.zeros(ws.value, dtype=torch.uint8, device=self.device)
         self._buffers["kv"] = torch.zeros(kv.value, dtype=torch.uint8, device=self.device)
+        # MXFP4: one layer's four projections in the packed bf16 layout -- what the prefill path widens a layer's codes into
+        self._buffers.pop("prefill_scratch", None)
+        if self.weight_format == "mxfp4":
+            hd = self.head_dim
+            total = 0
+            for n_rows, k in (((self.n_heads + 2 * self.n_kv_heads) * hd, self.hidden), (self.hidden, self.n_heads * hd),
+                              (2 * self.intermediate, self.hidden), (self.hidden, self.intermediate)):
+                nbytes = ctypes.c_size_t(0)
+                self._ck(self.lib.lsk_packed_bytes(n_rows, k, ctypes.byref(nbytes)))
+                total += nbytes.value
+            self._buffers["prefill_scratch"] = torch.empty(total, dtype=torch.uint8, device=self.device)
         cos, sin = self._rope_tables(self.max_ctx)
         self._buffers["cos"], self._buffers["sin"] = cos, sin
         torch.cuda.synchronize(self.device)
@@ -375,8 +413,11 @@ class HipEngine:
 
     def _bind_weights(self) -> None:
         handle = self._handle
-        if self._fp8:           # (the default format makes no call the parent ABI did not make)
+        if self.weight_format != "bf16":           # (the default format makes no call the parent ABI did not make)
             self._ck(self.lib.lsk_engine_set_weight_format(handle, _lib.WEIGHT_FORMATS[self.weight_format]))
+        if self.weight_format == "mxfp4":
+            scratch = self._buffers["prefill_scratch"]
+            self._ck(self.lib.lsk_engine_set_prefill_scratch(handle, scratch.data_ptr(), scratch.numel()))
         for i, packed in enumerate(self._packed):
             if packed is None:
                 continue
@@ -731,16 +772,20 @@ class HipEngine:
         hd = self.head_dim
         qdim, kvdim = self.n_heads * hd, self.n_kv_heads * hd
         eb = self.elem_bytes
-        if self._fp8:           # 1-byte codes + one fp32 power of two per packed row (the lm_head's rows pad to a whole tile)
-            size = lambda n, k: _round_up(n, 16) * (k + 4)       # noqa: E731
+        fp8_size = lambda n, k: _round_up(n, 16) * (k + 4)       # noqa: E731 -- 1-byte codes + one fp32 power of two per packed row
+        if self._fp8:           # (the lm_head's rows pad to a whole tile)
+            size = fp8_size
+        elif self.weight_format == "mxfp4":     # 4-bit codes + the exponent table (a row padded to whole dwords, 16 bytes behind it)
+            size = lambda n, k: _round_up(n, 16) * (k // 2 + _round_up(k // 32, 4)) + 16       # noqa: E731
         else:
             size = lambda n, k: eb * n * k                         # noqa: E731
+        head_size = fp8_size if self.weight_format == "mxfp4" else size
         return {
             "qkv": size(qdim + 2 * kvdim, self.hidden),
             "o": size(self.hidden, qdim),
             "gate_up": size(2 * self.intermediate, self.hidden),
             "down": size(self.hidden, self.intermediate),
-            "lm_head": size(self.vocab, self.hidden),
+            "lm_head": head_size(self.vocab, self.hidden),
         }
 
 
