@@ -45,7 +45,8 @@ extern "C" {
                              6: opt-in FP8 (e4m3) weight storage (lsk_packed_bytes_fp8, lsk_pack_linear_fp8, lsk_engine_set_weight_format,
                              lsk_engine_set_layer_prefill); version 6 also covers the opt-in MXFP4 weight storage, whose entry
                              points are additive (lsk_packed_bytes_mxfp4, lsk_pack_linear_mxfp4, lsk_engine_set_prefill_scratch,
-                             LSK_WEIGHT_FORMAT_MXFP4) */
+                             LSK_WEIGHT_FORMAT_MXFP4), and the scoring entry points, additive too (lsk_score_scratch_bytes,
+                             lsk_score_rows, lsk_score) */
 #define LSK_MAX_ROWS 16
 #define LSK_MAX_SPEC 15   /* num_speculations handled by one fused step (rows = spec + 1) */
 #define LSK_MAX_EOS 1024   /* eos + stop token ids of one generation (generator_base.py:106); ids outside the vocabulary are dropped by the host */
@@ -366,6 +367,27 @@ int lsk_ar_generate_sampled(lsk_engine* e, const int32_t* input_ids, int32_t n_i
                             const int32_t* eos_token_ids, int32_t n_eos, int32_t max_steps, float temperature, int32_t top_k,
                             float top_p, uint64_t seed, uint64_t offset, void* scratch, size_t scratch_bytes,
                             int32_t* out_tokens, int32_t* n_out, void* stream);
+/* ---- scoring on the device (csrc/lsk_score.h): what log-probability does the model, at an exit layer, give these tokens? ----
+ * The reference answers through lm_eval (eval.py: _loglikelihood_tokens, :165-331 -- `log_softmax(model(inp).logits)` :296-298, the
+ * continuation tokens gathered :309-312, the argmax compared with them :301-305).  Here, for a row l[0..V) of fp32 logits and a
+ * target t:  argmax = the index of the row maximum (lowest index on exact ties, as the greedy head picks);
+ * logprob = (l[t] - max) - log(sum_j exp(l[j] - max)) in fp32.  -inf entries are legal (they add 0; a target at -inf scores -inf; a
+ * row of nothing but -inf is undefined); a target outside [0, V) scores NaN.  Columns >= V of a row are never read.  Deterministic: a
+ * row's outputs do not depend on m, on its place in the block, on ld or on the launch.
+ * lsk_score_scratch_bytes: device scratch of the two calls below (a 16-row fp32 logits stage, and the partials and result arrays of
+ * the longest sequence the engine prefills: depends on vocab and max_prompt, not on max_ctx); needs no GPU.
+ * lsk_score_rows: the building block over ANY m <= LSK_MAX_ROWS rows of device logits [m][ld] fp32 (lsk_run_head's, or logits a
+ * processor has edited): targets DEVICE int32[m] -> logprob_out DEVICE fp32[m], argmax_out DEVICE int32[m].  Asynchronous.
+ * lsk_score: ids[0..n) (host, n >= 2, n - 1 <= max_prompt) scored at every exit layer of layer_ends (strictly increasing, in
+ * [1, num_layers], at most 8): the context is reset, ids[0..n-1) are prefilled ONCE (the last id is only a target, eval.py:256),
+ * and after layers [0, layer_ends[k]) every row's head -- final norm + lm_head on the exit hidden, forward_early's head
+ * (llama_model_utils.py:271-273); `forward`'s at num_layers (:204-205) -- is scored against the next id.  out_logprob: HOST
+ * fp32 [n_ends][n-1], out_argmax: HOST int32 [n_ends][n-1] (position i predicts ids[i+1]).  Synchronous at return; leaves kv_len 0. */
+int lsk_score_scratch_bytes(const lsk_config* cfg, size_t* out_bytes);
+int lsk_score_rows(lsk_engine* e, const void* logits, int32_t ld, int32_t m, const int32_t* targets, void* logprob_out,
+                   int32_t* argmax_out, void* scratch, size_t scratch_bytes, void* stream);
+int lsk_score(lsk_engine* e, const int32_t* ids, int32_t n, const int32_t* layer_ends, int32_t n_ends, float* out_logprob,
+              int32_t* out_argmax, void* scratch, size_t scratch_bytes, void* stream);
 /* Final RMSNorm + lm_head (+ greedy argmax) over rows [row_base, row_base+m)
  * (llama_model_utils.py:204-205, :271-273, :386-387; decode_next_token :120-122).
  * logits_out: optional device fp32 [m][ld_logits] (values are bf16-rounded like the model dtype);

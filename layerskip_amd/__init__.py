@@ -7,12 +7,12 @@ from .strategy_api import (GenerationConfig, GenerationResult, GenerationStrateg
                            GenerationStrategyResult, TokenGenerator)
 
 __all__ = ["GenerationConfig", "GenerationResult", "GenerationStrategy", "GenerationStrategyResult",
-           "TokenGenerator", "HipEngine", "get_engine", "HipSelfSpeculativeGenerationStrategy",
+           "TokenGenerator", "HipEngine", "get_engine", "ScoreResult", "HipSelfSpeculativeGenerationStrategy",
            "HipAutoRegressiveGenerationStrategy"]
 
 
 def __getattr__(name):
-    if name in ("HipEngine", "get_engine"):
+    if name in ("HipEngine", "get_engine", "ScoreResult"):
         from . import engine
         return getattr(engine, name)
     if name in ("HipSelfSpeculativeGenerationStrategy", "HipAutoRegressiveGenerationStrategy", "STRATEGIES"):

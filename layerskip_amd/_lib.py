@@ -12,6 +12,8 @@ from ctypes import POINTER, c_char_p, c_float, c_int32, c_size_t, c_uint64, c_vo
 LSK_MAX_ROWS = 16
 LSK_MAX_SPEC = 15
 LSK_MAX_EOS = 1024
+LSK_SCORE_MAX_ENDS = 8        # exit layers one lsk_score call scores
+LSK_SCORE_SPLIT = 4096        # consecutive logits of a row one workgroup of the scoring kernel holds (csrc/lsk_score.h)
 LSK_ABI_VERSION = 6
 LSK_OPT_BIG_THRESHOLD = 1
 LSK_OPT_TARGET_WGS = 2
@@ -112,6 +114,10 @@ PROTOTYPES = {
                                       c_size_t, POINTER(c_int32), c_void_p]),
     "lsk_ar_generate_sampled": (c_int32, [c_void_p, POINTER(c_int32), c_int32, c_int32, POINTER(c_int32), c_int32, c_int32, c_float, c_int32,
                                           c_float, c_uint64, c_uint64, c_void_p, c_size_t, POINTER(c_int32), POINTER(c_int32), c_void_p]),
+    "lsk_score_scratch_bytes": (c_int32, [POINTER(LskConfig), POINTER(c_size_t)]),
+    "lsk_score_rows": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "lsk_score": (c_int32, [c_void_p, POINTER(c_int32), c_int32, POINTER(c_int32), c_int32, POINTER(c_float), POINTER(c_int32), c_void_p,
+                            c_size_t, c_void_p]),
     "lsk_read_rows": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "lsk_write_rows": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "lsk_time_gateup": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_float), c_void_p]),

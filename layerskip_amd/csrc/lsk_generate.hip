@@ -6,6 +6,7 @@
 #include "lsk_engine.h"
 #include "lsk_accept.h"
 #include "lsk_sample.h"      // the sampling kernels and their launchers; needs the LSK_RES_* result-block layout of lsk_accept.h
+#include "lsk_score.h"       // log-probability + argmax of logits rows, and their launchers
 
 // Upload what a step needs from the host (the prompt rows / a changed input token / a changed eos list).
 static int upload_step_inputs(lsk_engine* e, const int32_t* input_ids, int P, const int32_t* eos_token_ids, int n_eos, hipStream_t st) {
@@ -642,4 +643,91 @@ extern "C" int lsk_pipeline_residual(lsk_engine* e, void* result_dev, int32_t re
                              (hipStream_t)stream);
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+// ---- scoring entry points (lsk_score.h) --------------------------------------------------------------------
+#define LSK_SCORE_MAX_ENDS 8
+// the caller-owned scratch: 16-row fp32 logits stage | partials of max(max_prompt, 16) rows | log-probabilities [8][max_prompt] | argmax [8][max_prompt]
+struct ScoreScratch { size_t stage, parts, logprob, argmax, total; int ld; };
+static ScoreScratch score_scratch(const lsk_config& c) {
+    ScoreScratch s;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) / 256 * 256; return o; };
+    s.ld = sampling_ld(c);
+    s.stage = take(sizeof(float) * (size_t)LSK_MAX_ROWS * s.ld);
+    s.parts = take(lsk_score_parts_bytes(c.vocab, c.max_prompt > LSK_MAX_ROWS ? c.max_prompt : LSK_MAX_ROWS));
+    s.logprob = take(sizeof(float) * (size_t)LSK_SCORE_MAX_ENDS * c.max_prompt);
+    s.argmax = take(sizeof(int) * (size_t)LSK_SCORE_MAX_ENDS * c.max_prompt);
+    s.total = off;
+    return s;
+}
+
+extern "C" int lsk_score_scratch_bytes(const lsk_config* cfg, size_t* out_bytes) {
+    LSK_TRY(lsk_check_cfg(cfg));
+    if (!out_bytes) return lsk_fail("null out");
+    *out_bytes = score_scratch(*cfg).total;
+    return 0;
+}
+
+static int check_score_scratch(lsk_engine* e, const void* scratch, size_t scratch_bytes, ScoreScratch* out) {
+    if (!scratch || ((size_t)scratch & 15)) return lsk_fail("scoring scratch: null or not 16-byte aligned");
+    *out = score_scratch(e->cfg);
+    if (scratch_bytes < out->total) return lsk_fail("scoring scratch too small: %zu < %zu", scratch_bytes, out->total);
+    return 0;
+}
+
+extern "C" int lsk_score_rows(lsk_engine* e, const void* logits, int32_t ld, int32_t m, const int32_t* targets, void* logprob_out,
+                              int32_t* argmax_out, void* scratch, size_t scratch_bytes, void* stream) {
+    LSK_TRY(lsk_ready(e));
+    if (!logits || !targets || !logprob_out || !argmax_out) return lsk_fail("lsk_score_rows: null pointer");
+    if (m < 1 || m > LSK_MAX_ROWS || ld < e->cfg.vocab) return lsk_fail("lsk_score_rows: m=%d ld=%d out of range", m, ld);
+    ScoreScratch ss;
+    LSK_TRY(check_score_scratch(e, scratch, scratch_bytes, &ss));
+    void* parts = (unsigned char*)scratch + ss.parts;
+    LSK_TRY(launch_score_part((const float*)logits, ld, e->cfg.vocab, m, targets, parts, (hipStream_t)stream));
+    return launch_score_finalize(e->cfg.vocab, m, targets, parts, (float*)logprob_out, argmax_out, (hipStream_t)stream);
+}
+
+extern "C" int lsk_score(lsk_engine* e, const int32_t* ids, int32_t n, const int32_t* layer_ends, int32_t n_ends, float* out_logprob,
+                         int32_t* out_argmax, void* scratch, size_t scratch_bytes, void* stream) {
+    LSK_TRY(lsk_ready(e));
+    const lsk_config& c = e->cfg;
+    hipStream_t st = (hipStream_t)stream;
+    if (!ids || !layer_ends || !out_logprob || !out_argmax) return lsk_fail("lsk_score: null pointer");
+    if (n < 2 || n - 1 > c.max_prompt) return lsk_fail("lsk_score: %d ids out of range 2..%d", n, c.max_prompt + 1);
+    if (n - 1 > c.max_ctx) return lsk_fail("lsk_score: positions exceed max_ctx");
+    if (n_ends < 1 || n_ends > LSK_SCORE_MAX_ENDS) return lsk_fail("lsk_score: %d exit layers out of range 1..%d", n_ends, LSK_SCORE_MAX_ENDS);
+    for (int k = 0; k < n_ends; ++k)
+        if (layer_ends[k] < 1 || layer_ends[k] > c.num_layers || (k > 0 && layer_ends[k] <= layer_ends[k - 1]))
+            return lsk_fail("lsk_score: layer_ends must be strictly increasing in [1, %d] (entry %d is %d)", c.num_layers, k, layer_ends[k]);
+    LSK_TRY(lsk_layers_bound(e, 0, layer_ends[n_ends - 1]));
+    LSK_TRY(lsk_check_ids(e, ids, n));
+    ScoreScratch ss;
+    LSK_TRY(check_score_scratch(e, scratch, scratch_bytes, &ss));
+    const int rows = n - 1;                                       // the last id is only a target (eval.py:256)
+    float* stage = (float*)((unsigned char*)scratch + ss.stage);
+    unsigned char* parts = (unsigned char*)scratch + ss.parts;
+    float* lp = (float*)((unsigned char*)scratch + ss.logprob);
+    int* am = (int*)((unsigned char*)scratch + ss.argmax);
+    LSK_TRY(lsk_engine_reset(e, stream));
+    HIP_OK(hipMemcpyAsync(e->bulk_ids, ids, sizeof(int) * n, hipMemcpyHostToDevice, st));
+    LSK_TRY(lsk_embed_rows_dev(e, e->bulk_ids, rows, e->hbulk, st));
+    int done = 0;
+    for (int k = 0; k < n_ends; ++k) {
+        // the prompt runs through every layer once, whatever the number of exit layers
+        LSK_TRY(lsk_run_bulk_dev(e, rows, &e->state->kv_len, done, layer_ends[k], st));
+        done = layer_ends[k];
+        // forward_early's head on the exit hiddens (final norm + lm_head, llama_model_utils.py:271-273); the rows are only read.  Each
+        // 16-row pass leaves its rows' partials; the whole sequence is finalized once
+        for (int r0 = 0; r0 < rows; r0 += LSK_MAX_ROWS) {
+            const int m = (rows - r0) < LSK_MAX_ROWS ? (rows - r0) : LSK_MAX_ROWS;
+            LSK_TRY(lsk_run_head_dev(e, e->hbulk + (size_t)r0 * c.hidden, m, stage, ss.ld, nullptr, st));
+            LSK_TRY(launch_score_part(stage, ss.ld, c.vocab, m, e->bulk_ids + r0 + 1, parts + lsk_score_parts_bytes(c.vocab, r0), st));
+        }
+        LSK_TRY(launch_score_finalize(c.vocab, rows, e->bulk_ids + 1, parts, lp + (size_t)k * rows, am + (size_t)k * rows, st));
+    }
+    HIP_OK(hipMemcpyAsync(out_logprob, lp, sizeof(float) * (size_t)n_ends * rows, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(out_argmax, am, sizeof(int) * (size_t)n_ends * rows, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return 0;                                                     // nothing advanced the context: kv_len is 0
 }

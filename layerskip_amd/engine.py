@@ -36,6 +36,25 @@ class StepResult:
     verified_tokens: List[int]
 
 
+@dataclass
+class ScoreResult:
+    """What ``HipEngine.score`` returns: position i of row k is the model's prediction for ``ids[i + 1]`` after layers
+    ``[0, layer_ends[k])`` (final norm + lm_head on that hidden state)."""
+    ids: List[int]
+    layer_ends: List[int]
+    logprobs: torch.Tensor      # fp32 [E, n - 1]: log-probability of ids[1:]
+    argmax: torch.Tensor        # int32 [E, n - 1]: the greedy token at each position
+
+    @property
+    def greedy(self) -> torch.Tensor:
+        """bool [E, n - 1]: the greedy token is the next id (eval.py:301-305's `max_equal`, per position)."""
+        return self.argmax == torch.tensor(self.ids[1:], dtype=torch.int32)
+
+    def nll(self, k: int = -1) -> float:
+        """Mean negative log-likelihood per token at ``layer_ends[k]`` (perplexity = exp of it)."""
+        return float(-self.logprobs[k].double().mean())
+
+
 def _round_up(v: int, a: int) -> int:
     return (v + a - 1) // a * a
 
@@ -379,6 +398,7 @@ class HipEngine:
         self._ck(self.lib.lsk_workspace_bytes(ctypes.byref(self.cfg), ctypes.byref(ws)))
         self._ck(self.lib.lsk_kv_pool_bytes(ctypes.byref(self.cfg), ctypes.byref(kv)))
         self._buffers.pop("sampling", None)
+        self._buffers.pop("score", None)
         self._buffers["ws"] = torch.zeros(ws.value, dtype=torch.uint8, device=self.device)
         self._buffers["kv"] = torch.zeros(kv.value, dtype=torch.uint8, device=self.device)
         # MXFP4: one layer's four projections in the packed bf16 layout -- what the prefill path widens a layer's codes into
@@ -651,6 +671,50 @@ class HipEngine:
         scratch = self._sampling_scratch()
         self._ck(self.lib.lsk_pipeline_residual(self._handle, block.data_ptr(), block.numel(), int(src_row), _u64(seed), _u64(offset),
                                              scratch.data_ptr(), scratch.numel(), self._stream))
+
+    # ------------------------------------------------------------------ scoring (lsk_score.h)
+    def _score_scratch(self) -> torch.Tensor:
+        buf = self._buffers.get("score")
+        if buf is None:
+            n = ctypes.c_size_t(0)
+            self._ck(self.lib.lsk_score_scratch_bytes(ctypes.byref(self.cfg), ctypes.byref(n)))
+            buf = torch.empty(n.value, dtype=torch.uint8, device=self.device)
+            self._buffers["score"] = buf
+        return buf
+
+    def score_rows(self, logits: torch.Tensor, targets: torch.Tensor):
+        """Log-probability of ``targets[r]`` under row r of device logits [m, ld] (fp32, m <= 16) and the row's argmax (lowest index
+        on ties).  Returns (logprob fp32[m], argmax int32[m]) on the device; columns >= vocab of a row are never read."""
+        if logits.dtype != torch.float32 or logits.device != self.device or logits.dim() != 2 or logits.stride(1) != 1:
+            raise _lib.LskError("logits must be a [m, ld] fp32 tensor on the engine device")
+        m, ld = logits.shape[0], (logits.stride(0) if logits.shape[0] > 1 else max(logits.stride(0), logits.shape[1]))
+        if targets.dtype != torch.int32 or targets.device != self.device or targets.shape != (m,) or not targets.is_contiguous():
+            raise _lib.LskError("targets must be a contiguous int32 tensor [m] on the engine device")
+        scratch = self._score_scratch()
+        lp = torch.empty(m, dtype=torch.float32, device=self.device)
+        am = torch.empty(m, dtype=torch.int32, device=self.device)
+        self._ck(self.lib.lsk_score_rows(self._handle, logits.data_ptr(), ld, m, targets.data_ptr(), lp.data_ptr(), am.data_ptr(),
+                                      scratch.data_ptr(), scratch.numel(), self._stream))
+        return lp, am
+
+    def score(self, ids: Sequence[int], layer_ends: Optional[Sequence[int]] = None) -> ScoreResult:
+        """Teacher-forced scores of ``ids`` (n >= 2) at the exit layers ``layer_ends`` (strictly increasing, at most 8; default: the
+        whole model) in one call: one prefill, then every position's head scored against the next id on the device (lsk_score).
+        The cached context is dropped; kv_len is 0 afterwards."""
+        ids = [int(t) for t in ids]
+        ends = [int(e) for e in (layer_ends if layer_ends is not None else [self.num_layers])]
+        n = len(ids)
+        if n < 2:
+            raise _lib.LskError("score: at least two ids (a context token and a target)")
+        self.ensure_capacity(n - 1, n - 1)
+        scratch = self._score_scratch()
+        lp = torch.empty(max(1, len(ends)), n - 1, dtype=torch.float32)
+        am = torch.empty(max(1, len(ends)), n - 1, dtype=torch.int32)
+        self._ck(self.lib.lsk_score(self._handle, _i32_array(ids), n, _i32_array(ends), len(ends),
+                                 ctypes.cast(lp.data_ptr(), ctypes.POINTER(ctypes.c_float)),
+                                 ctypes.cast(am.data_ptr(), ctypes.POINTER(ctypes.c_int32)),
+                                 scratch.data_ptr(), scratch.numel(), self._stream))
+        return ScoreResult(ids, ends, lp[: len(ends)], am[: len(ends)])
 
     def logits_rows(self, blocks: Sequence[Sequence[int]]) -> torch.Tensor:
         """Final norm + lm_head logits of the listed (buffer, row_base, count) blocks -> [rows, vocab] in the model dtype (the values
