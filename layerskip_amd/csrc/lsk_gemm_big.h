@@ -20,7 +20,8 @@
 #include "lsk_common.h"
 #include "lsk_gemm.h"      // the weight formats (LSK_WF_*) and the e4m3 -> bf16 conversion of the decode kernel
 
-#define LSK_BIG_BK 64
+#include "lsk_big_shapes.h"   // LSK_BIG_BK (64 features per K-tile) and the host-side shape rules
+#define LSK_BIG_FOLD_KT 8        // fp32 build: K-tiles per block sum (a power of two, a multiple of every ring depth)
 #define LSK_BIG_LDA (64 * LSK_EB + 32)   // bytes per LDS row: 64 elements + 32 B pad (bf16: slot (10r + g) mod 16, conflict-free A-fragment reads)
 
 struct BigGemmParams {
@@ -184,6 +185,18 @@ __global__ __launch_bounds__(NW * KS * 64, 2) void lsk_gemm_big_kernel(const Big
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < NTW; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // fp32 build: K is summed in blocks of LSK_BIG_FOLD_KT K-tiles (512 features), the block sums into a second accumulator.  One fp32
+    // accumulator walking K in order carries ~sqrt(K) / 4.9 ulp of rounding noise (measured 18.3 ulp on K rows at K = 8192, where torch's
+    // fp32 GEMM has 10.4 at 131 rows); blocks leave ~sqrt(1 / blocks + 1 / 512) of it (measured 5.5).  32 more registers, no scratch
+    // (DESIGN.md 3.4).  The 16-bit builds round the sum to 8 or 11 bits anyway and keep one accumulator: their code is unchanged.
+    constexpr bool FOLD = LSK_EB == 4;
+    [[maybe_unused]] f32x4 tot[FOLD ? MT : 1][FOLD ? NTW : 1];
+    if constexpr (FOLD) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NTW; ++j) tot[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
 
     // Weight fragments: a register ring PB K-tiles deep per wave, refilled the moment a slot is consumed.  Activations:
     // two register sets (tiles kt+1, kt+2) feeding the double-buffered LDS image.  Slot indices are static: the K loop is
@@ -243,6 +256,20 @@ __global__ __launch_bounds__(NW * KS * 64, 2) void lsk_gemm_big_kernel(const Big
             store_a(cur ^ 1, aq[cur ^ 1]);                    // tile kt + 1 (loaded one iteration ago) -> the other LDS buffer
             __syncthreads();
         }
+        if constexpr (FOLD) {
+            if (((kt0 + PB) & (LSK_BIG_FOLD_KT - 1)) == 0) {       // (wave-uniform; PB divides LSK_BIG_FOLD_KT)
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < NTW; ++nt) { tot[mt][nt] += acc[mt][nt]; acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+            }
+        }
+    }
+    if constexpr (FOLD) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NTW; ++nt) acc[mt][nt] += tot[mt][nt];      // (the ragged last block: zero when K is whole blocks)
     }
     if (KS > 1) {
         // the second group's partial sums: through LDS (the activation images are dead: the loop's last barrier is behind every wave),

@@ -6,6 +6,7 @@
 #include "../../include/layerskip_hip.h"
 #include "lsk_host.h"
 #include "lsk_gemm_big.h"
+#include "lsk_big_shapes.h"   // big_qkv_shape, big_resid_shape, big_ring_depth: the pure rules the switches below turn into instances
 
 // What lsk_gemm_big_kernel assumes of the model: it walks K in runs of >= 2 K-tiles (a weight ring two K-tiles deep is the shallowest),
 // so the K of every projection -- hidden, n_heads * head_dim, intermediate -- is a multiple of 2 * LSK_BIG_BK.  (Every N is whole
@@ -67,7 +68,8 @@ static BigGemmParams big_swiglu(const lsk_config& c, const elem_t* x, int M, con
 //                 above (launch_big_resid).
 // WF = the weight format of p.wp.  The rules are functions of the projection and the prompt length alone: the FP8 instances take the SAME
 // shape, ring depth and K-split as the model-dtype ones (same K order: the bit-identity of the two formats rests on it).
-// Each rule is a pure choice (big_qkv_shape, big_resid_shape: what the benchmark tool prints) and a switch from it to the instance.
+// Each rule is a pure choice (big_qkv_shape, big_resid_shape in lsk_big_shapes.h: what the benchmark tool prints) and a switch from it
+// to the instance.
 template <int EPI, int NTW, int MT, int PB, int NW, bool PIN, int KS, bool TR, int WF>
 static int launch_big_pb(const BigGemmParams& p, hipStream_t st) {
     const dim3 grid(lsk_big_grid<NTW, MT, NW>(p.M, p.n_tiles));            // XCD-aware 1-D map: lsk_gemm_big.h
@@ -75,9 +77,6 @@ static int launch_big_pb(const BigGemmParams& p, hipStream_t st) {
     HIP_OK(hipGetLastError());
     return 0;
 }
-
-// PB = the deepest weight ring of {PBMAX, 2} that divides the number of K-tiles of a K-split group (K is a multiple of 128: big_gemm_ok)
-static int big_ring_depth(int pbmax, int K, int ks) { return (pbmax == 4 && (K / LSK_BIG_BK / ks) % 4 == 0) ? 4 : 2; }
 
 template <int WF, int EPI, int NTW, int MT, int PBMAX, int NW, bool PIN, int KS = 1, bool TR = true>
 static int launch_big(const BigGemmParams& p, hipStream_t st) {
@@ -95,33 +94,6 @@ static int launch_big(const BigGemmParams& p, hipStream_t st) {
 #define LSK_BIG_BY_FORMAT(rule, p, st) \
     ((p).wfmt == LSK_WF_ELEM ? rule<LSK_WF_ELEM>(p, st) : lsk_fail("prefill: FP8 weight storage exists in the bf16 library only"))
 #endif
-
-// Tile shape per launch from the WORKGROUP COUNTS each shape would give (round 6, second pass: tools/gemm_big_bench.hip with
-// LSK_BENCH_EXPLORE=1 at 127 .. 4095 rows, profiles/r06_gemm_big_bench_explore.txt).  A CU sustains ~3.5 TFLOP/s on these kernels once it
-// holds two waves per SIMD, whatever the tile, so the choice is about balance: the biggest tile that still gives every CU work, and never a
-// count that leaves half the chip a second round to itself (128 x 256 at 1023 rows of a 12 288-feature q/k/v: 384 workgroups at one per
-// CU, 133 us against 114 for 512 workgroups of 128 x 192).
-enum BigQkvShape { BIG_QKV_64x128, BIG_QKV_64x192, BIG_QKV_128x192, BIG_QKV_128x256, BIG_QKV_128x384 };   // (the order of the cost table; the fp32 build has one shape per projection)
-static BigQkvShape big_qkv_shape(int M, int n_tiles) {
-    // cost of a shape = (workgroups on the busiest CU) x (tile area) / (TFLOP/s a CU sustains on that shape), the rates read off the table:
-    // ~3.7-3.8 for the eight-wave tiles, 3.45 for 128-row four-wave tiles once a CU holds two of them (2.85 alone: one wave per SIMD),
-    // 2.2-2.8 for 64-row tiles.  llama2-7B (N = 12 288): 64 x 128 up to 191 rows, 64 x 192 to 319, 128 x 192 to 639, 128 x 384 where it is
-    // whole rounds (1023 rows: 256 workgroups, 147.1 -> 102.3 us = 1 006 TFLOP/s; 2047: 512, 260.6 -> 211.0), 128 x 256 / 128 x 192 between.
-    struct Shape { int bm, tiles; float alone, shared; };
-    static const Shape shapes[5] = {{64, 8, 1.75f, 2.3f}, {64, 12, 2.15f, 2.8f}, {128, 12, 2.85f, 3.45f}, {128, 16, 3.7f, 3.7f}, {128, 24, 3.8f, 3.8f}};
-    int best = 0;
-    float best_cost = 0.f;
-    for (int i = 0; i < 5; ++i) {
-        const Shape& sh = shapes[i];
-        const int wgs = ((M + sh.bm - 1) / sh.bm) * ((n_tiles + sh.tiles - 1) / sh.tiles);
-        const int per_cu = (wgs + 255) / 256;
-        float rate = per_cu == 1 ? sh.alone : sh.shared;
-        if (i == 0 && per_cu >= 3) rate = 2.65f;
-        const float cost = (float)per_cu * (float)(sh.bm * sh.tiles) / rate;
-        if (i == 0 || cost <= best_cost) { best = i; best_cost = cost; }        // ties go to the bigger tile
-    }
-    return (BigQkvShape)best;
-}
 
 template <int WF>
 static int launch_big_qkv_wf(const BigGemmParams& p, hipStream_t st) {
@@ -148,29 +120,6 @@ static int launch_big_gateup_wf(const BigGemmParams& p, hipStream_t st) {
 #endif
 }
 static int launch_big_gateup(const BigGemmParams& p, hipStream_t st) { return LSK_BIG_BY_FORMAT(launch_big_gateup_wf, p, st); }
-
-// (row tile x column tile; KS2 = K-split 2; the last is the only shape with a ring-4 form)
-enum BigResidShape { BIG_RESID_KS2_32x128, BIG_RESID_KS2_64x128, BIG_RESID_KS2_128x128, BIG_RESID_128x256, BIG_RESID_128x128, BIG_RESID_64x128 };
-static BigResidShape big_resid_shape(int M, int n_tiles, int K) {
-    const int panels = (n_tiles + 7) / 8;
-    const int rb128 = (M + 127) / 128;
-    // N = hidden is few panels: while a shape gives <= one workgroup per CU, K-split 2 (eight waves per workgroup, the two halves of K side
-    // by side: two waves per SIMD instead of one) with the SMALLEST row tile that still does -- 32 rows up to 255 prompt rows of a
-    // 4096-wide model (down 67.5 -> 58.2 us), 64 up to 511 (round 6, first pass), 128 up to 1023 (down 135.5 -> 106.3).  The two groups
-    // need an even number of ring-depth-2 K-tile pairs each: K a multiple of 256.
-    if ((K / LSK_BIG_BK) % 4 == 0) {
-        if (((M + 31) / 32) * panels <= 256) return BIG_RESID_KS2_32x128;
-        if (((M + 63) / 64) * panels <= 256) return BIG_RESID_KS2_64x128;
-        if (rb128 * panels <= 256) return BIG_RESID_KS2_128x128;
-    }
-    // beyond that 128 x 256 tiles of eight waves (pinned activation requests) wherever their count is at most one round or at least two
-    // (2047 rows: o_proj 72.6 -> 65.0 us, down 218.9 -> 183.1), 128 x 128 in between (3071 rows: 384 of them would leave half the chip a
-    // second round)
-    const int w256 = rb128 * ((n_tiles + 15) / 16);
-    if (rb128 * panels > 256 && (w256 <= 256 || w256 >= 512)) return BIG_RESID_128x256;
-    if (rb128 * panels >= 512) return BIG_RESID_128x128;
-    return BIG_RESID_64x128;
-}
 
 template <int WF>
 static int launch_big_resid_wf(const BigGemmParams& p, hipStream_t st) {

