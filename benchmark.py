@@ -101,7 +101,7 @@ def main(argv=None, backend_factory=None):
     ctx = setup(args, syn)                                        # benchmark.py:218 (seeds, process group under torchrun)
     partition = run_partition(args, syn, gen.exit_layer if gen.generation_strategy.startswith("self_speculative") else -1, ctx)
     model, tokenizer = load_model_and_tokenizer(args, syn, gen.exit_layer, ctx, partition)
-    strategy = make_strategy(gen, ctx, partition, backend_factory, weight_format=syn.weight_format)
+    strategy = make_strategy(gen, ctx, partition, backend_factory, weight_format=syn.weight_format, draft_weight_format=syn.draft_weight_format)
     metrics = run_on_rank0(ctx, strategy, model, lambda: benchmark(model, tokenizer, b, gen, syn, args.seed, strategy))
     if metrics is None:
         return None                                               # ranks > 0: served, nothing to report

@@ -43,9 +43,9 @@ def main(argv=None, backend_factory=None):
     model, tokenizer = load_model_and_tokenizer(args, syn, gen.exit_layer, ctx, partition)
     spec_cfg = replace(gen, generation_strategy="self_speculative")
     ar_cfg = replace(gen, generation_strategy="autoregressive", exit_layer=-1)
-    spec_strategy = make_strategy(spec_cfg, ctx, partition, backend_factory, weight_format=syn.weight_format)
+    spec_strategy = make_strategy(spec_cfg, ctx, partition, backend_factory, weight_format=syn.weight_format, draft_weight_format=syn.draft_weight_format)
     spec = TokenGenerator(tokenizer, model, spec_strategy)
-    ar = TokenGenerator(tokenizer, model, make_strategy(ar_cfg, ctx, partition, backend_factory, weight_format=syn.weight_format))
+    ar = TokenGenerator(tokenizer, model, make_strategy(ar_cfg, ctx, partition, backend_factory, weight_format=syn.weight_format, draft_weight_format=syn.draft_weight_format))
     out = run_on_rank0(ctx, spec_strategy, model, lambda: compare(model, tokenizer, b, syn, spec, ar, spec_cfg, ar_cfg, seed))
     if out is None:
         return 0                                                  # ranks > 0

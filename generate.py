@@ -53,7 +53,7 @@ def main(argv=None, lines=None, backend_factory=None):
     ctx = setup(args, syn)               # generate.py:41-52 -- under torchrun every rank stays and owns a layer range
     partition = run_partition(args, syn, gen.exit_layer if gen.generation_strategy.startswith("self_speculative") else -1, ctx)
     model, tokenizer = load_model_and_tokenizer(args, syn, gen.exit_layer, ctx, partition)
-    strategy = make_strategy(gen, ctx, partition, backend_factory, weight_format=syn.weight_format)
+    strategy = make_strategy(gen, ctx, partition, backend_factory, weight_format=syn.weight_format, draft_weight_format=syn.draft_weight_format)
     generator = TokenGenerator(tokenizer, model, strategy)
     streamer = transformers.TextStreamer(tokenizer) if tokenizer is not None else None
     return run_on_rank0(ctx, strategy, model, lambda: repl(generator, tokenizer, model, gen, streamer, lines))

@@ -46,7 +46,8 @@ extern "C" {
                              lsk_engine_set_layer_prefill); version 6 also covers the opt-in MXFP4 weight storage, whose entry
                              points are additive (lsk_packed_bytes_mxfp4, lsk_pack_linear_mxfp4, lsk_engine_set_prefill_scratch,
                              LSK_WEIGHT_FORMAT_MXFP4), and the scoring entry points, additive too (lsk_score_scratch_bytes,
-                             lsk_score_rows, lsk_score) */
+                             lsk_score_rows, lsk_score), and the draft copies, additive too (lsk_engine_set_layer_draft,
+                             lsk_engine_set_draft_head) */
 #define LSK_MAX_ROWS 16
 #define LSK_MAX_SPEC 15   /* num_speculations handled by one fused step (rows = spec + 1) */
 #define LSK_MAX_EOS 1024   /* eos + stop token ids of one generation (generator_base.py:106); ids outside the vocabulary are dropped by the host */
@@ -178,6 +179,25 @@ int lsk_engine_set_layer(lsk_engine* e, int32_t layer, const void* wqkv, const v
 int lsk_engine_set_weight_format(lsk_engine* e, int32_t weight_format);
 int lsk_engine_set_prefill_scratch(lsk_engine* e, void* scratch, size_t scratch_bytes);
 int lsk_engine_set_layer_prefill(lsk_engine* e, int32_t layer, const void* wqkv, const void* wo, const void* wgu, const void* wdown);
+/* ---- draft copies: draft from quantised weights, verify in the model dtype; opt-in, bf16 library only (the fp16 / fp32 libraries
+ * export the symbols and return an error).  The engine's own format must be LSK_WEIGHT_FORMAT_ELEM.
+ * lsk_engine_set_layer_draft binds a SECOND set of a layer's four projection buffers in `weight_format` = LSK_WEIGHT_FORMAT_FP8_E4M3
+ * or LSK_WEIGHT_FORMAT_MXFP4 (the layouts of lsk_pack_linear_fp8 / lsk_pack_linear_mxfp4; the norm gains are shared); all four
+ * buffers, or four NULLs to unbind the layer (weight_format is then ignored).  lsk_engine_set_draft_head binds a copy of the lm_head in
+ * the FP8 layout (NULL unbinds).  Either call drops the captured step graphs.
+ * While any of them is bound, the speculation steps (lsk_spec_step, lsk_spec_generate, their sampled forms, the captured steps) take
+ * another shape: the num_speculations one-row draft passes run layers [0, exit_layer) and the head from the copies; then the input
+ * token and the drafts are embedded again and ALL num_speculations + 1 rows run through ALL layers from the model-dtype weights,
+ * rewriting the early layers' KV of their positions; the prompt rows of a first step run all layers from the model-dtype weights.
+ * Every KV slot below the context length, every verified logit and every emitted token is then computed by the model-dtype kernels
+ * alone, whose rows do not depend on how many rows ride with them: greedy ids are the ids of the engine without copies, bit for bit,
+ * on any checkpoint; only the acceptance rate can move.  Such a step needs the copies on every layer of [0, exit_layer) and the
+ * draft head: a step whose exit_layer exceeds the leading layers that have copies is refused.
+ * Everything else -- lsk_ar_*, lsk_score, lsk_run_layers, lsk_run_bulk, lsk_run_head, lsk_draft_block* and the pipeline entry
+ * points -- ignores the copies. */
+int lsk_engine_set_layer_draft(lsk_engine* e, int32_t layer, int32_t weight_format, const void* wqkv, const void* wo, const void* wgu,
+                               const void* wdown);
+int lsk_engine_set_draft_head(lsk_engine* e, const void* lm_head_fp8);
 /* embed: plain bf16 [V][H]; final_norm: bf16 [H]; lm_head: PACKED [V][H] -- each may be NULL on a pipeline rank that never embeds a
  * token / runs a head (a middle rank: checkpoint.load_layer_range(embed=False, head=False)); the entry points that need them say so;
  * rope_cos / rope_sin: bf16 [rope_len][head_dim/2] (host-precomputed exactly as

@@ -64,6 +64,8 @@ PROTOTYPES = {
     "lsk_engine_set_weight_format": (c_int32, [c_void_p, c_int32]),
     "lsk_engine_set_prefill_scratch": (c_int32, [c_void_p, c_void_p, c_size_t]),
     "lsk_engine_set_layer_prefill": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lsk_engine_set_layer_draft": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lsk_engine_set_draft_head": (c_int32, [c_void_p, c_void_p]),
     "lsk_engine_create": (c_int32, [POINTER(LskConfig), c_void_p, c_size_t, c_void_p, c_size_t, POINTER(c_void_p)]),
     "lsk_engine_destroy": (c_int32, [c_void_p]),
     "lsk_engine_set_layer": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -34,6 +34,7 @@ class SyntheticArguments:
     pp_balance: str = "draft"          # multi-GPU (torchrun) layer split: "draft" | "memory" (layerskip_amd.pipeline.plan_partition)
     weight_format: str = "bf16"        # "fp8_e4m3": projections stored as e4m3 codes + one power of two per row (layerskip_amd/quant.py)
                                        # "mxfp4": q/k/v/o/gate/up/down as e2m1 codes + one power of two per 32-feature block, lm_head FP8
+    draft_weight_format: Optional[str] = None   # "fp8_e4m3" | "mxfp4": quantised copies for the draft passes only; the emitted ids stay the bf16 engine's
 
 
 def setup(args: Arguments, syn: SyntheticArguments):
@@ -98,10 +99,13 @@ def load_model_and_tokenizer(args: Arguments, syn: SyntheticArguments, exit_laye
     return model, tokenizer
 
 
-def make_strategy(cfg: GenerationConfig, ctx=None, partition=None, backend_factory=None, weight_format: str = "bf16"):
+def make_strategy(cfg: GenerationConfig, ctx=None, partition=None, backend_factory=None, weight_format: str = "bf16",
+                  draft_weight_format: Optional[str] = None):
     name = cfg.generation_strategy.replace("_hip", "")
     # (the default format passes no keyword: the engines are built exactly as before)
     engine_kwargs = {"weight_format": weight_format} if weight_format != "bf16" else None
+    if draft_weight_format:             # every strategy of a run gets it, so that they share one engine (autoregressive decoding ignores the copies)
+        engine_kwargs = dict(engine_kwargs or {}, draft_weight_format=draft_weight_format)
     if ctx is not None:
         from ..pipeline_strategy import PIPELINE_STRATEGIES
         if name not in PIPELINE_STRATEGIES:

@@ -12,6 +12,10 @@ struct LayerWeights {
     // FP8 weight format, optional (lsk_engine_set_layer_prefill): model-dtype packed copies of the DEQUANTISED projections.  A layer that has
     // them prefills from them with the model-dtype kernels; a layer without (the default) prefills from the codes above
     const elem_t *pf_wqkv = nullptr, *pf_wo = nullptr, *pf_wgu = nullptr, *pf_wdown = nullptr;
+    // draft copies, optional (lsk_engine_set_layer_draft): the projections once more in a quantised format (draft_format: FP8 or MXFP4).
+    // Only the one-row draft passes of a speculation step read them; everything that is kept -- KV, logits, tokens -- comes from the above
+    const elem_t *dr_wqkv = nullptr, *dr_wo = nullptr, *dr_wgu = nullptr, *dr_wdown = nullptr;
+    int draft_format = 0;
 };
 
 struct lsk_engine {
@@ -20,6 +24,8 @@ struct lsk_engine {
     const elem_t *embed = nullptr, *final_norm = nullptr, *lm_head = nullptr, *rope_cos = nullptr, *rope_sin = nullptr;
     int rope_len = 0;
     int weight_format = 0;        // LSK_WEIGHT_FORMAT_*: what wqkv / wo / wgu / wdown / lm_head point at (lsk_engine_set_weight_format)
+    int draft_layers_bound = 0;           // layers that have draft copies
+    const elem_t* draft_head = nullptr;   // FP8 copy of the lm_head for the draft passes (lsk_engine_set_draft_head)
     elem_t* pf_scratch = nullptr; // MXFP4: caller-owned scratch of one layer's four projections in the packed model-dtype layout (prefill)
     // device workspace carve
     unsigned char* ws = nullptr;
@@ -99,11 +105,16 @@ int lsk_layers_bound(lsk_engine* e, int lb, int le);
 int lsk_set_kv_len_dev(lsk_engine* e, int kv_len, bool add, hipStream_t st);
 int lsk_check_ids(lsk_engine* e, const int32_t* ids, int n);
 int lsk_embed_rows_dev(lsk_engine* e, const int* tokens_dev, int n, elem_t* dst, hipStream_t st);
-// decoder layers [lb, le) in place over m <= 16 rows of `x` (positions *base_ptr + pos_off + i)
-int lsk_run_layers_dev(lsk_engine* e, elem_t* x, int m, const int* base_ptr, int pos_off, int lb, int le, hipStream_t st);
+void lsk_drop_graphs(lsk_engine* e);
+// draft copies (lsk_engine_set_layer_draft / lsk_engine_set_draft_head): is any bound; the leading layers [0, n) that have them
+bool lsk_draft_bound(const lsk_engine* e);
+int lsk_draft_covered(const lsk_engine* e);
+// decoder layers [lb, le) in place over m <= 16 rows of `x` (positions *base_ptr + pos_off + i); draft: from the layers' draft copies
+int lsk_run_layers_dev(lsk_engine* e, elem_t* x, int m, const int* base_ptr, int pos_off, int lb, int le, hipStream_t st, bool draft = false);
 // final norm + lm_head + argmax over rows of x; tokens land in tokens_dev[0..m); embed_dst: the chosen token's embedding row
 // kv_add > 0: the argmax launch also advances the verified context length by kv_add (device counter and host mirror)
+// draft: the FP8 draft head in place of the engine's lm_head
 int lsk_run_head_dev(lsk_engine* e, const elem_t* x, int m, float* logits, int ld_logits, int* tokens_dev, hipStream_t st,
-                     elem_t* embed_dst = nullptr, int kv_add = 0);
+                     elem_t* embed_dst = nullptr, int kv_add = 0, bool draft = false);
 // rows [0, n) of the bulk buffer through layers [lb, le)
 int lsk_run_bulk_dev(lsk_engine* e, int n, const int* base_ptr, int lb, int le, hipStream_t st);

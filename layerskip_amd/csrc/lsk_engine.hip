@@ -258,7 +258,7 @@ extern "C" int lsk_engine_destroy(lsk_engine* e) {
     if (e->host_result) (void)hipHostFree(e->host_result);
     if (e->host_sums) (void)hipHostFree(e->host_sums);
     for (int i = 0; i < 2; ++i) if (e->step_done[i]) (void)hipEventDestroy(e->step_done[i]);
-    for (auto& g : e->graphs) (void)hipGraphExecDestroy(g.exec);
+    lsk_drop_graphs(e);
     if (e->fork_ev) (void)hipEventDestroy(e->fork_ev);
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
     delete e;
@@ -282,12 +282,64 @@ extern "C" int lsk_engine_set_weight_format(lsk_engine* e, int32_t weight_format
 #if LSK_ELEM_DTYPE != 0
     if (weight_format != LSK_WEIGHT_FORMAT_ELEM) return lsk_fail("lsk_engine_set_weight_format: FP8 / MXFP4 weight storage exists in the bf16 library only");
 #endif
-    if (weight_format != e->weight_format) {                    // captured steps carry the kernel instances of the old format
-        for (auto& g : e->graphs) (void)hipGraphExecDestroy(g.exec);
-        e->graphs.clear();
-    }
+    if (weight_format != LSK_WEIGHT_FORMAT_ELEM && lsk_draft_bound(e))
+        return lsk_fail("lsk_engine_set_weight_format: draft copies are bound; they go with the model-dtype format only");
+    if (weight_format != e->weight_format) lsk_drop_graphs(e);  // captured steps carry the kernel instances of the old format
     e->weight_format = weight_format;
     return 0;
+}
+
+void lsk_drop_graphs(lsk_engine* e) {
+    for (auto& g : e->graphs) (void)hipGraphExecDestroy(g.exec);
+    e->graphs.clear();
+}
+
+bool lsk_draft_bound(const lsk_engine* e) { return e->draft_head != nullptr || e->draft_layers_bound > 0; }
+
+int lsk_draft_covered(const lsk_engine* e) {
+    int n = 0;
+    while (n < e->cfg.num_layers && e->layers[n].dr_wqkv != nullptr) ++n;
+    return n;
+}
+
+// the draft copies exist beside model-dtype weights only: what is kept of a step is computed from those
+static int draft_setter_ok(lsk_engine* e, const char* who) {
+    if (!e) return lsk_fail("%s: null engine", who);
+    if (e->weight_format != LSK_WEIGHT_FORMAT_ELEM)
+        return lsk_fail("%s: the engine's own weight format is %d; draft copies go with the model-dtype format (0) only", who, e->weight_format);
+    return 0;
+}
+
+extern "C" int lsk_engine_set_layer_draft(lsk_engine* e, int32_t layer, int32_t weight_format, const void* wqkv, const void* wo, const void* wgu,
+                                          const void* wdown) {
+#if LSK_ELEM_DTYPE == 0
+    LSK_TRY(draft_setter_ok(e, "lsk_engine_set_layer_draft"));
+    if (layer < 0 || layer >= e->cfg.num_layers) return lsk_fail("lsk_engine_set_layer_draft: bad layer %d", layer);
+    const int bound = (wqkv != nullptr) + (wo != nullptr) + (wgu != nullptr) + (wdown != nullptr);
+    if (bound != 0 && bound != 4) return lsk_fail("lsk_engine_set_layer_draft: null weight (all four buffers, or four NULLs to unbind the layer's copies)");
+    if (bound == 4 && weight_format != LSK_WEIGHT_FORMAT_FP8_E4M3 && weight_format != LSK_WEIGHT_FORMAT_MXFP4)
+        return lsk_fail("lsk_engine_set_layer_draft: draft copies are FP8 (%d) or MXFP4 (%d), not format %d", LSK_WEIGHT_FORMAT_FP8_E4M3,
+                        LSK_WEIGHT_FORMAT_MXFP4, weight_format);
+    lsk_drop_graphs(e);                                         // captured steps carry the step shape and the buffers of the old binding
+    LayerWeights& lw = e->layers[layer];
+    e->draft_layers_bound += (bound == 4) - (lw.dr_wqkv != nullptr);
+    lw.dr_wqkv = (const elem_t*)wqkv; lw.dr_wo = (const elem_t*)wo; lw.dr_wgu = (const elem_t*)wgu; lw.dr_wdown = (const elem_t*)wdown;
+    lw.draft_format = bound == 4 ? weight_format : 0;
+    return 0;
+#else
+    return lsk_fail("lsk_engine_set_layer_draft: quantised draft copies exist in the bf16 library only");
+#endif
+}
+
+extern "C" int lsk_engine_set_draft_head(lsk_engine* e, const void* lm_head_fp8) {
+#if LSK_ELEM_DTYPE == 0
+    LSK_TRY(draft_setter_ok(e, "lsk_engine_set_draft_head"));
+    lsk_drop_graphs(e);
+    e->draft_head = (const elem_t*)lm_head_fp8;
+    return 0;
+#else
+    return lsk_fail("lsk_engine_set_draft_head: quantised draft copies exist in the bf16 library only");
+#endif
 }
 
 extern "C" int lsk_engine_set_layer_prefill(lsk_engine* e, int32_t layer, const void* wqkv, const void* wo, const void* wgu, const void* wdown) {
@@ -393,10 +445,7 @@ extern "C" int lsk_engine_set_block_table(lsk_engine* e, const int32_t* table, i
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
     bool identity = true;
     for (int i = 0; i < n_pages; ++i) identity = identity && table[i] == i;
-    if (identity != e->block_table_identity) {       // captured steps carry the flag in their attention launches' arguments
-        for (auto& g : e->graphs) (void)hipGraphExecDestroy(g.exec);
-        e->graphs.clear();
-    }
+    if (identity != e->block_table_identity) lsk_drop_graphs(e);   // captured steps carry the flag in their attention launches' arguments
     e->block_table_identity = identity;
     return 0;
 }
@@ -513,34 +562,39 @@ static int run_gemm(lsk_engine* e, int cat, GemmLaunch<PRO, EPI> g, int target_w
 #define LSK_HEAD_WGS 0
 #endif
 // decoder layers [lb, le) in place over rows of `x` (positions *base_ptr + pos_off + i)
-int lsk_run_layers_dev(lsk_engine* e, elem_t* x, int m, const int* base_ptr, int pos_off, int lb, int le, hipStream_t st) {
+int lsk_run_layers_dev(lsk_engine* e, elem_t* x, int m, const int* base_ptr, int pos_off, int lb, int le, hipStream_t st, bool draft) {
     const lsk_config& c = e->cfg;
-    const int wf = e->weight_format;
     for (int l = lb; l < le; ++l) {
         const LayerWeights& lw = e->layers[l];
+        // draft: the same launches from the layer's draft copies, in their format (the norm gains are shared)
+        if (draft && lw.dr_wqkv == nullptr) return lsk_fail("layer %d has no draft copies (lsk_engine_set_layer_draft)", l);
+        const elem_t *wqkv = draft ? lw.dr_wqkv : lw.wqkv, *wo = draft ? lw.dr_wo : lw.wo, *wgu = draft ? lw.dr_wgu : lw.wgu,
+                     *wdown = draft ? lw.dr_wdown : lw.wdown;
+        const int wf = draft ? lw.draft_format : e->weight_format;
         elem_t* kpool = e->kv_pool + (size_t)l * e->kv_layer_elems;
         elem_t* vpool = kpool + e->kv_half_elems;
-        LSK_TRY(run_gemm(e, LSK_PROF_QKV, gemm_qkv(c, x, m, lw.wqkv, lw.norm1, e->rope_cos, e->rope_sin, base_ptr, pos_off, e->block_table,
+        LSK_TRY(run_gemm(e, LSK_PROF_QKV, gemm_qkv(c, x, m, wqkv, lw.norm1, e->rope_cos, e->rope_sin, base_ptr, pos_off, e->block_table,
                                                    e->qbuf, kpool, vpool, wf), e->target_wgs, st));
         LSK_TRY(launch_attn(e, e->qbuf, e->attn, kpool, vpool, m, pos_off, st));
-        LSK_TRY(run_gemm(e, LSK_PROF_OPROJ, gemm_resid(e->attn, m, c.n_heads * c.head_dim, lw.wo, c.hidden, x, wf),
+        LSK_TRY(run_gemm(e, LSK_PROF_OPROJ, gemm_resid(e->attn, m, c.n_heads * c.head_dim, wo, c.hidden, x, wf),
                          LSK_OPROJ_WGS > 0 ? LSK_OPROJ_WGS : e->target_wgs, st));
-        LSK_TRY(run_gemm(e, LSK_PROF_GATEUP, gemm_swiglu(c, x, m, lw.wgu, lw.norm2, e->act, wf), LSK_GATEUP_WGS > 0 ? LSK_GATEUP_WGS : e->target_wgs, st));
-        LSK_TRY(run_gemm(e, LSK_PROF_DOWN, gemm_resid(e->act, m, c.intermediate, lw.wdown, c.hidden, x, wf), e->target_wgs, st));
+        LSK_TRY(run_gemm(e, LSK_PROF_GATEUP, gemm_swiglu(c, x, m, wgu, lw.norm2, e->act, wf), LSK_GATEUP_WGS > 0 ? LSK_GATEUP_WGS : e->target_wgs, st));
+        LSK_TRY(run_gemm(e, LSK_PROF_DOWN, gemm_resid(e->act, m, c.intermediate, wdown, c.hidden, x, wf), e->target_wgs, st));
     }
     return 0;
 }
 
 // final norm + lm_head + argmax over rows of x; tokens land in tokens_dev[0..m)
 int lsk_run_head_dev(lsk_engine* e, const elem_t* x, int m, float* logits, int ld_logits, int* tokens_dev, hipStream_t st,
-                     elem_t* embed_dst, int kv_add) {
+                     elem_t* embed_dst, int kv_add, bool draft) {
+    if (draft && !e->draft_head) return lsk_fail("the draft head is not bound on this engine (lsk_engine_set_draft_head)");
     if (!e->lm_head || !e->final_norm) return lsk_fail("the final norm / lm_head are not bound on this engine (a middle pipeline rank runs no head)");
     if (embed_dst != nullptr && !e->embed) return lsk_fail("the embedding is not bound on this engine");
     // sample=True (tokens_dev == nullptr): the logits rows are what the caller wants, nobody reads an argmax
     if (tokens_dev == nullptr && kv_add) return lsk_fail("internal: a head without an argmax launch cannot advance the context");
-    // (the lm_head of an MXFP4 engine is stored in the FP8 format)
-    const int head_wf = e->weight_format == LSK_WEIGHT_FORMAT_MXFP4 ? LSK_WF_FP8 : e->weight_format;
-    GemmLaunch<PRO_RMS, EPI_HEAD> g = gemm_head(e->cfg, x, m, e->lm_head, e->final_norm, logits, ld_logits, e->part_val, e->part_idx, head_wf);
+    // (the lm_head of an MXFP4 engine is stored in the FP8 format, and so is the draft head)
+    const int head_wf = (draft || e->weight_format == LSK_WEIGHT_FORMAT_MXFP4) ? LSK_WF_FP8 : e->weight_format;
+    GemmLaunch<PRO_RMS, EPI_HEAD> g = gemm_head(e->cfg, x, m, draft ? e->draft_head : e->lm_head, e->final_norm, logits, ld_logits, e->part_val, e->part_idx, head_wf);
     hipEvent_t ea = nullptr, eb = nullptr;
     LSK_TRY(profile_pair(e, LSK_PROF_HEAD, m, gemm_stream_bytes(g.p), &ea, &eb));
     LSK_TRY(launch_head(g, LSK_HEAD_WGS > 0 ? LSK_HEAD_WGS : e->target_wgs, e->max_parts, tokens_dev, e->embed, embed_dst,

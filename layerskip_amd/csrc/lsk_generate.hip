@@ -45,9 +45,9 @@ struct StepSampling {
 // drawn, not maximised) and launch_sample draws with tags tag0.. at sm->offset, leaving the warped distributions in `probs`; a head
 // without an argmax launch cannot advance the context, so kv_add must be 0.
 static int head_token(lsk_engine* e, const elem_t* x, int m, int* tokens_dev, elem_t* embed_dst, int kv_add, hipStream_t st,
-                      const StepSampling* sm, int tag0, float* probs) {
-    if (sm == nullptr) return lsk_run_head_dev(e, x, m, nullptr, 0, tokens_dev, st, embed_dst, kv_add);
-    LSK_TRY(lsk_run_head_dev(e, x, m, sm->logits, sm->ld, nullptr, st, nullptr, kv_add));
+                      const StepSampling* sm, int tag0, float* probs, bool draft = false) {
+    if (sm == nullptr) return lsk_run_head_dev(e, x, m, nullptr, 0, tokens_dev, st, embed_dst, kv_add, draft);
+    LSK_TRY(lsk_run_head_dev(e, x, m, sm->logits, sm->ld, nullptr, st, nullptr, kv_add, draft));
     // (lsk_engine_set_globals accepts a NULL embedding -- a pipeline rank that embeds nothing; a draw that is to leave its token's embedding
     // row behind needs one)
     if (embed_dst != nullptr && !e->embed) return lsk_fail("sample=True: the embedding is not bound on this engine (only rank 0 of a pipeline drafts)");
@@ -78,23 +78,31 @@ static int enqueue_step_body(lsk_engine* e, int P, int S, int E, int n_eos, int 
     const int L = c.num_layers;
     if (e->kv_len_host + P + S > c.max_ctx) return lsk_fail("context overflow: %d + %d + %d > max_ctx %d", e->kv_len_host, P, S, c.max_ctx);
     const int* kvp = &e->state->kv_len;
-    // ---- forward_early over the prompt rows that are not the last one (LMU:213-276, rows 0..P-2) ----
+    // Draft copies bound (lsk_engine_set_layer_draft, validate_step_args: they cover [0, E) and the draft head is there): the S draft
+    // passes read the quantised copies and nothing they leave is kept -- the verify block runs ALL layers from the model-dtype weights
+    // and rewrites the early layers' KV of its positions, so every KV slot below kv_len, every verified logit and every emitted token
+    // is computed by the model-dtype kernels alone.
+    const bool dq = lsk_draft_bound(e);
+    // ---- forward_early over the prompt rows that are not the last one (LMU:213-276, rows 0..P-2); dq: all L layers at once ----
     if (P > 1) {
         LSK_TRY(lsk_embed_rows_dev(e, e->bulk_ids, P - 1, e->hbulk, st));
-        LSK_TRY(lsk_run_bulk_dev(e, P - 1, kvp, 0, E, st));
+        LSK_TRY(lsk_run_bulk_dev(e, P - 1, kvp, 0, dq ? L : E, st));
     }
     // ---- draft loop (SSG:127-148), device resident: row j = input token (j = 0) or draft j ----
     for (int j = 0; j <= S; ++j) {
         elem_t* xr = e->hrow + (size_t)j * c.hidden;
+        if (j == S && dq) break;           // the early pass of the last draft belongs to the verify block
         if (j == 0) LSK_TRY(lsk_embed_rows_dev(e, e->row_tokens, 1, xr, st));   // rows j > 0 were embedded by the previous head
-        LSK_TRY(lsk_run_layers_dev(e, xr, 1, kvp, P - 1 + j, 0, E, st));   // j == S: forward_remainder's early pass (LMU:350-362)
+        LSK_TRY(lsk_run_layers_dev(e, xr, 1, kvp, P - 1 + j, 0, E, st, dq));   // j == S: forward_remainder's early pass (LMU:350-362)
         // draft j + 1 -> row_tokens[j + 1], its embedding -> the next row (sampled: RNG tag j, its distribution -> p_draft row j)
         if (j < S)
-            LSK_TRY(head_token(e, xr, 1, e->row_tokens + j + 1, xr + c.hidden, 0, st, sm, j, sm ? sm->p_draft + (size_t)j * sm->ld : nullptr));
+            LSK_TRY(head_token(e, xr, 1, e->row_tokens + j + 1, xr + c.hidden, 0, st, sm, j, sm ? sm->p_draft + (size_t)j * sm->ld : nullptr, dq));
     }
     // ---- forward_remainder, late layers (LMU:364-383): exit_query_cache rows + last draft row ----
-    if (P > 1) LSK_TRY(lsk_run_bulk_dev(e, P - 1, kvp, E, L, st));
-    LSK_TRY(lsk_run_layers_dev(e, e->hrow, S + 1, kvp, P - 1, E, L, st));
+    // dq: the step rows hold draft-format exit hiddens, dead by now; the input token and the drafts are embedded again from the device ids
+    if (dq) LSK_TRY(lsk_embed_rows_dev(e, e->row_tokens, S + 1, e->hrow, st));
+    if (P > 1 && !dq) LSK_TRY(lsk_run_bulk_dev(e, P - 1, kvp, E, L, st));
+    LSK_TRY(lsk_run_layers_dev(e, e->hrow, S + 1, kvp, P - 1, dq ? 0 : E, L, st));
     LSK_TRY(head_token(e, e->hrow, S + 1, e->verified, nullptr, 0, st, sm, LSK_TAG_VERIFY, sm ? sm->p_verify : nullptr));
     // ---- accept + rollback (SSG:186-221) ----
     int* dres = e->result + slot * 64;
@@ -154,6 +162,10 @@ static int validate_step_args(lsk_engine* e, int P, int S, int E, const int32_t*
     if (S < 0 || S > LSK_MAX_SPEC) return lsk_fail("num_speculations %d out of range 0..%d", S, LSK_MAX_SPEC);
     if (E < 1 || E > c.num_layers) return lsk_fail("exit_layer %d out of range 1..%d", E, c.num_layers);
     LSK_TRY(lsk_layers_bound(e, 0, c.num_layers));
+    if (lsk_draft_bound(e)) {              // a step drafts from the copies or not at all: never from a mixture
+        if (E > lsk_draft_covered(e)) return lsk_fail("exit_layer %d exceeds the %d leading layers that have draft copies (lsk_engine_set_layer_draft)", E, lsk_draft_covered(e));
+        if (!e->draft_head) return lsk_fail("draft copies are bound on %d layers but the draft head is not (lsk_engine_set_draft_head)", lsk_draft_covered(e));
+    }
     if (n_eos < 0 || n_eos > LSK_MAX_EOS) return lsk_fail("n_eos %d out of range 0..%d", n_eos, LSK_MAX_EOS);
     if (n_eos > 0 && !eos_token_ids) return lsk_fail("null eos_token_ids");
     return 0;

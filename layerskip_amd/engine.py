@@ -96,10 +96,22 @@ class HipEngine:
 
     def __init__(self, model, max_ctx: int = 2048, max_prompt: int = 1024, page_size: int = 128,
                  target_wgs: int = 0, layer_range: Optional[Sequence[int]] = None, release_weights: bool = False,
-                 weight_format: str = "bf16"):
+                 weight_format: str = "bf16", draft_weight_format: Optional[str] = None, draft_layers: Optional[int] = None):
         cfg = model.config
         if weight_format not in _lib.WEIGHT_FORMATS:
             raise _lib.LskError(f"unknown weight_format {weight_format!r} ({' | '.join(_lib.WEIGHT_FORMATS)})")
+        if draft_weight_format is not None:
+            if draft_weight_format not in ("fp8_e4m3", "mxfp4"):
+                raise _lib.LskError(f"unknown draft_weight_format {draft_weight_format!r} (fp8_e4m3 | mxfp4)")
+            if weight_format != "bf16":
+                raise _lib.LskError(f"draft_weight_format={draft_weight_format!r} needs weight_format='bf16', not {weight_format!r}: "
+                                    "the copies are for drafting, what is kept comes from the bf16 weights")
+            if layer_range is not None:
+                raise _lib.LskError("draft_weight_format is a one-GPU option: a layer-range engine (pipeline rank) takes no draft copies")
+            if draft_layers is not None and not (1 <= int(draft_layers) <= cfg.num_hidden_layers):
+                raise _lib.LskError(f"draft_layers={draft_layers} out of range 1..{cfg.num_hidden_layers}")
+        elif draft_layers is not None:
+            raise _lib.LskError("draft_layers needs a draft_weight_format")
         # (the final norm is the one tensor every rank of a pipeline materialises: a middle rank holds neither the embedding nor the head)
         weight = model.model.norm.weight if model.model.embed_tokens.weight.is_meta else model.model.embed_tokens.weight
         dmap = getattr(model, "hf_device_map", None)
@@ -129,6 +141,15 @@ class HipEngine:
             raise _lib.LskError(f"weight_format={weight_format!r} needs a bf16 model; this one is {dtype_name} "
                                 "(FP8 weight storage exists in the bf16 build only)")
         self.weight_format = weight_format
+        # draft_weight_format="fp8_e4m3" | "mxfp4" (opt-in; None = off): quantised COPIES of the projections of layers [0, draft_layers)
+        # (default: every layer) and an FP8 copy of the lm_head, read by the one-row draft passes of a speculation step only.  The
+        # verify block then runs all layers from the bf16 weights and rewrites the early layers' KV, so KV, verified logits and emitted
+        # tokens are the plain engine's bit for bit -- on any checkpoint; only acceptance moves.
+        if draft_weight_format is not None and dtype_name != "bf16":
+            raise _lib.LskError(f"draft_weight_format={draft_weight_format!r} needs a bf16 model; this one is {dtype_name} "
+                                "(quantised draft copies exist in the bf16 build only)")
+        self.draft_weight_format = draft_weight_format
+        self.draft_layers = (cfg.num_hidden_layers if draft_layers is None else int(draft_layers)) if draft_weight_format is not None else 0
         # what the MFMA-tiled prefill kernels read under FP8: the same codes as the decode kernels (their FP8 instances widen them in
         # the weight ring and scale the accumulators, csrc/lsk_gemm_big.h), so prompt KV and exit hiddens are the bf16 engine's on the
         # dequantised model and packed bytes are 0.5 x bf16's.  None in the default format.  One set of buffers serves both paths.
@@ -168,6 +189,7 @@ class HipEngine:
         self.release_weights = release_weights
         self._handle = ctypes.c_void_p(None)
         self._packed = []           # per-layer packed buffers (kept alive); None outside layer_range
+        self._packed_draft = []     # draft_weight_format: (wqkv, wo, wgu, wdown) copies of layers [0, draft_layers)
         self._packed_prefill = {}   # measurement only (_bind_prefill_copies): layer -> bf16-packed dequantised copies for the prefill kernels
         self._globals = {}
         self._buffers = {}
@@ -234,6 +256,7 @@ class HipEngine:
         with torch.cuda.device(self.device):
             self._bind_prefill_copies(list(self._packed_prefill), bind=False)      # (copies of the old values, if a tool bound any)
             self._packed = []
+            self._packed_draft = []
             self._globals = {}
             self._pack_weights(model)
             self._bind_weights()
@@ -297,11 +320,14 @@ class HipEngine:
     def packed_weight_bytes(self) -> dict:
         """Bytes of the packed projection buffers (this engine's layers and its lm_head): "decode" -- the buffers the decode path reads,
         which in the bf16 and FP8 formats are the ones prefill reads too; "prefill_only" -- buffers that only the prefill kernels read
-        (0); and, on an MXFP4 engine only, "prefill_scratch" -- the layer-sized bf16 scratch it widens one layer at a time into."""
+        (0); on an MXFP4 engine only, "prefill_scratch" -- the layer-sized bf16 scratch it widens one layer at a time into; and, with
+        draft_weight_format only, "draft" -- the quantised copies the draft passes read and the FP8 draft head."""
         bufs = [t for pk in self._packed if pk is not None for t in pk[:4]]
         bufs += [self._globals["lm_head"]] if self._globals.get("lm_head") is not None else []
         out = {"decode": sum(t.numel() for t in bufs),
                "prefill_only": sum(t.numel() for pk in self._packed_prefill.values() for t in pk)}
+        if self.draft_weight_format is not None:         # the draft copies and the FP8 draft head
+            out["draft"] = sum(t.numel() for pk in self._packed_draft for t in pk) + self._globals["draft_head"].numel()
         if self._buffers.get("prefill_scratch") is not None:
             out["prefill_scratch"] = self._buffers["prefill_scratch"].numel()
         return out
@@ -354,6 +380,8 @@ class HipEngine:
             n1 = layer.input_layernorm.weight.detach().contiguous()
             n2 = layer.post_attention_layernorm.weight.detach().contiguous()
             self._packed.append(self._pack_projections(layer, self.weight_format) + (n1, n2))
+            if idx < self.draft_layers:
+                self._packed_draft.append(self._pack_projections(layer, self.draft_weight_format))
             if self.release_weights:
                 torch.cuda.synchronize(self.device)
                 for lin in (a.q_proj, a.k_proj, a.v_proj, a.o_proj, mlp.gate_proj, mlp.up_proj, mlp.down_proj):
@@ -366,6 +394,10 @@ class HipEngine:
             head = self._packed_buffer(self.vocab, H, self._head_format)
             self._pack_into(head, m.lm_head.weight, 0, 1, 0, self._head_format, _round_up(self.vocab, 16))
             self._globals["lm_head"] = head
+            if self.draft_weight_format is not None:
+                dhead = self._packed_buffer(self.vocab, H, "fp8_e4m3")
+                self._pack_into(dhead, m.lm_head.weight, 0, 1, 0, "fp8_e4m3", _round_up(self.vocab, 16))
+                self._globals["draft_head"] = dhead
             tied = have_embed and m.lm_head.weight.data_ptr() == m.model.embed_tokens.weight.data_ptr()
             if self.release_weights and not tied:
                 torch.cuda.synchronize(self.device)
@@ -450,6 +482,19 @@ class HipEngine:
         ptr = lambda t: t.data_ptr() if t is not None else None          # noqa: E731 -- NULL: not bound on this rank
         self._ck(self.lib.lsk_engine_set_globals(handle, ptr(g["embed"]), ptr(g["final_norm"]), ptr(g["lm_head"]),
                                               self._buffers["cos"].data_ptr(), self._buffers["sin"].data_ptr(), self.max_ctx))
+        if self.draft_weight_format is not None:
+            self.bind_draft_copies(True)
+
+    def bind_draft_copies(self, bind: bool = True) -> None:
+        """Bind (the state after construction) or unbind the draft copies of a draft_weight_format engine: unbound, its steps are the
+        plain engine's.  Either way the captured step graphs are dropped (lsk_engine_set_layer_draft)."""
+        if self.draft_weight_format is None:
+            raise _lib.LskError("bind_draft_copies: this engine was built without draft_weight_format")
+        fmt = _lib.WEIGHT_FORMATS[self.draft_weight_format]
+        for i, pk in enumerate(self._packed_draft):
+            ptrs = [t.data_ptr() for t in pk] if bind else [None] * 4
+            self._ck(self.lib.lsk_engine_set_layer_draft(self._handle, i, fmt, *ptrs))
+        self._ck(self.lib.lsk_engine_set_draft_head(self._handle, self._globals["draft_head"].data_ptr() if bind else None))
 
     def ensure_capacity(self, total_tokens: int, prompt_len: int) -> None:
         """Grow the KV pool / prompt buffer if a request needs more (context is lost)."""
@@ -832,18 +877,20 @@ class HipEngine:
         return out
 
     # bytes one launch of each projection streams from HBM (algorithmic: the packed weights once)
-    def projection_bytes(self) -> dict:
+    def projection_bytes(self, weight_format: Optional[str] = None) -> dict:
+        """`weight_format`: another format's bytes for this geometry (the draft copies'); default: the engine's own."""
+        wf = weight_format or self.weight_format
         hd = self.head_dim
         qdim, kvdim = self.n_heads * hd, self.n_kv_heads * hd
         eb = self.elem_bytes
         fp8_size = lambda n, k: _round_up(n, 16) * (k + 4)       # noqa: E731 -- 1-byte codes + one fp32 power of two per packed row
-        if self._fp8:           # (the lm_head's rows pad to a whole tile)
+        if wf == "fp8_e4m3":    # (the lm_head's rows pad to a whole tile)
             size = fp8_size
-        elif self.weight_format == "mxfp4":     # 4-bit codes + the exponent table (a row padded to whole dwords, 16 bytes behind it)
+        elif wf == "mxfp4":     # 4-bit codes + the exponent table (a row padded to whole dwords, 16 bytes behind it)
             size = lambda n, k: _round_up(n, 16) * (k // 2 + _round_up(k // 32, 4)) + 16       # noqa: E731
         else:
             size = lambda n, k: eb * n * k                         # noqa: E731
-        head_size = fp8_size if self.weight_format == "mxfp4" else size
+        head_size = fp8_size if wf == "mxfp4" else size
         return {
             "qkv": size(qdim + 2 * kvdim, self.hidden),
             "o": size(self.hidden, qdim),
@@ -871,6 +918,8 @@ def get_engine(model, check_weights: bool = True, **kwargs) -> HipEngine:
         _ENGINES = weakref.WeakKeyDictionary()
     # one engine per (model, weight format): a request for one format is never served by an engine of the other
     fmt = kwargs.get("weight_format") or "bf16"
+    if kwargs.get("draft_weight_format"):        # ... and per draft format and depth; without the option the key is what it was
+        fmt = (fmt, kwargs["draft_weight_format"], kwargs.get("draft_layers"))
     per_model = _ENGINES.get(model)
     if per_model is None:
         per_model = _ENGINES[model] = {}

@@ -25,7 +25,9 @@ Execution paths:
         step i makes under the same torch seed).
   slow  logits processors or more than 15 speculations: the same kernels driven row-block by row-block with the
         logits materialised as a tensor so the user's callables see what the reference shows them (sampling, if
-        any, then happens on those logits with torch).
+        any, then happens on those logits with torch).  On an engine with draft copies (engine_kwargs draft_weight_format) this
+        path keeps the plain step shape: its building blocks read the bf16 weights, drafts included; only the fused, step and
+        sampled paths above draft from the copies.
 """
 from __future__ import annotations
 

@@ -34,6 +34,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
+from . import _lib
 from .hip_strategies import HipAutoRegressiveGenerationStrategy, HipSelfSpeculativeGenerationStrategy
 from .pipeline import PipelineSpeculativeDecoder, Sampling, plan_partition
 from .strategy_api import GenerationConfig, GenerationStrategy, GenerationStrategyResult
@@ -170,6 +171,9 @@ class HipPipelineSelfSpeculativeGenerationStrategy(GenerationStrategy):
         self.backend_factory = backend_factory or _hip_backend
         self.optimistic = optimistic
         self.engine_kwargs = engine_kwargs or {}
+        if self.engine_kwargs.get("draft_weight_format"):
+            # the pipeline's verify reuses rank 0's early-layer KV and exit hiddens; draft copies give that sharing up
+            raise _lib.LskError("draft_weight_format is a one-GPU option: a layer-range engine (pipeline rank) takes no draft copies")
         self._last = None
         self.last_steps: List[Tuple[int, int]] = []
 
